@@ -13,7 +13,14 @@ Timing: W untimed warmup steps, then exactly K steps bracketed by barrier +
 torch.cuda.synchronize() on both sides; the elapsed time is the MAX over ranks.  p50 latency
 is per batch, from submission to the top-5 results being available on the host.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B]
+A plain run does only what the headline figure needs: set up the pipeline, W warmup steps,
+the K timed steps, the result line.  ``--dump-outputs DIR`` also writes what the last timed
+step handed to its caller (the arrays of its result, e.g. ``top_prob`` / ``top_index``) as
+``DIR/<name>.npy``; models, pixels and audio are seeded, so equal arguments give equal inputs
+and two builds can be compared output for output.  ``--full`` is where measurements beyond the
+headline figure belong; the benchmark has none today, so it runs the same steps.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 """
 from __future__ import annotations
@@ -214,6 +221,14 @@ def parse_args(argv=None) -> argparse.Namespace:
     ap.add_argument("--pcie-gbps", type=float, default=50.0,
                     help="(pp, --ingest host) one rank's host->device rate the planner prices "
                          "the upload at (PCIe Gen5 x16 ~50 GB/s)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write the arrays the last timed step returned to "
+                         "its caller as DIR/<name>.npy (float32; float64 for 64-bit values, exact for "
+                         "integers up to 2^53; at most 64 MB in all, a fixed seeded sample of anything "
+                         "larger)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline figure (none today: the "
+                         "other models and configurations are runs of their own, --model / --parallel)")
     a = ap.parse_args(argv)
     explicit_hw = "--height" in (sys.argv[1:] if argv is None else argv)
     if (a.parallel == "pp" or a.model == "yolov8n") and not explicit_hw:
@@ -221,6 +236,35 @@ def parse_args(argv=None) -> argparse.Namespace:
     if a.batch is None:
         a.batch = 192 if a.model == "yolov8n" else 28 if a.model.startswith("whisper") else 640
     return a
+
+
+DUMP_LIMIT = 64 << 20     # --dump-outputs: bytes over all the arrays of one dump
+
+
+def dump_outputs(directory: str, tensors: dict) -> dict:
+    """``--dump-outputs``: the numeric arrays of one step's result as ``directory/<name>.npy``,
+    float32 (float64 for 64-bit values: integers are exact up to 2^53).  Past DUMP_LIMIT bytes in all, every array is cut to
+    its share as a fixed sample (seed 0, sorted flat indices), the same from run to run.
+    Returns {name: shape written}."""
+    import numpy as np
+    arrays = {}
+    for name, v in tensors.items():
+        if isinstance(v, torch.Tensor):
+            wide = v.dtype in (torch.float64, torch.int64)
+            arrays[str(name)] = v.detach().to("cpu", torch.float64 if wide else torch.float32).numpy()
+        elif isinstance(v, np.ndarray) and v.dtype.kind in "fiub":
+            arrays[str(name)] = v.astype(np.float64 if v.dtype.itemsize == 8 else np.float32)
+    total = sum(arr.nbytes for arr in arrays.values())
+    os.makedirs(directory, exist_ok=True)
+    written = {}
+    for name, arr in sorted(arrays.items()):
+        if total > DUMP_LIMIT:
+            keep = max(1, int(arr.size * DUMP_LIMIT / total))
+            index = np.sort(np.random.default_rng(0).choice(arr.size, keep, replace=False))
+            arr = arr.reshape(-1)[index]
+        np.save(os.path.join(directory, f"{name}.npy"), arr)
+        written[name] = list(arr.shape)
+    return written
 
 
 def main(argv=None):
@@ -279,6 +323,7 @@ def main(argv=None):
     frame_id = 0
     inflight: deque = deque()
     latencies: list = []
+    last = [None]             # --dump-outputs: the newest completed step's result
 
     def step(record):
         nonlocal frame_id
@@ -291,6 +336,8 @@ def main(argv=None):
         while len(inflight) > a.depth:
             res, rec = inflight.popleft()
             res.wait()
+            if a.dump_outputs:
+                last[0] = res
             if rec:
                 latencies.append(res.latency)
 
@@ -298,6 +345,8 @@ def main(argv=None):
         while inflight:
             res, rec = inflight.popleft()
             res.wait()
+            if a.dump_outputs:
+                last[0] = res
             if rec and record:
                 latencies.append(res.latency)
 
@@ -351,6 +400,8 @@ def main(argv=None):
             out["audio_seconds_per_s"] = round(ws * a.batch * a.chunk * a.steps / elapsed, 1)
             if a.transcribe:
                 out["decoded_tokens_per_s"] = round(ws * a.batch * a.transcribe * a.steps / elapsed, 1)
+        if a.dump_outputs and last[0] is not None:
+            out["outputs"] = dump_outputs(a.dump_outputs, last[0].wait())
         print(json.dumps(out), flush=True)
     D.barrier()
     D.destroy()
@@ -542,6 +593,7 @@ def _drive_pp(a, pipeline, plane, plan, responses, rank, ws):
     depth = max(a.depth, 2 * ws)
     state = {"frame_id": 0}
     latencies: list = []
+    last = [None, -1]         # --dump-outputs: result and frame id of the highest frame completed
 
     def run(n, record):
         sent = done = 0
@@ -559,6 +611,9 @@ def _drive_pp(a, pipeline, plane, plan, responses, rank, ws):
                 raise RuntimeError(f"pipeline frame failed: {info} {o}")
             res = o["topk"]
             res.wait()
+            # replicas answer out of order: the highest frame id, not the latest arrival
+            if a.dump_outputs and int(info["frame_id"]) > last[1]:
+                last[0], last[1] = res, int(info["frame_id"])
             if record:
                 latencies.append(res.latency)
     run(max(a.warmup, 3 * ws), False)          # every replica tunes + captures its graphs
@@ -580,6 +635,7 @@ def _drive_pp(a, pipeline, plane, plan, responses, rank, ws):
         if rank != 0:
             return None
     p50 = statistics.median(latencies) if latencies else 0.0
+    outputs = dump_outputs(a.dump_outputs, last[0].wait()) if a.dump_outputs and last[0] is not None else None
     return {
         "metric": METRIC, "value": round(frames / elapsed, 1), "unit": "frames/s", "n_gpus": ws,
         "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 3),
@@ -598,6 +654,7 @@ def _drive_pp(a, pipeline, plane, plan, responses, rank, ws):
                                                 / a.batch),
                    "boundary_ms": plan.predicted_ms.get("boundary_ms"),
                    "pipeline": "(SyntheticFrames FrameResize ResNet50Classifier ClassifierTopK)"},
+        **({"outputs": outputs} if outputs is not None else {}),
     }
 
 

@@ -1,8 +1,9 @@
 """Local pipeline engine: definitions, graph paths, name mapping, stream events, parameters.
 
-Where the reference checkout is present its example PipelineDefinitions (``examples/pipeline/
-*.json``, ``elements/media/text_pipeline_*.json``) are run unchanged as golden inputs;
-otherwise equivalent inline definitions are used.
+The files under ``tests/golden/definitions`` are this project's own definitions written the way
+definition files of the reference kind are (``"#"`` comment keys, ``aiko_services.*`` module
+names, ``class_name`` reuse, an inspector writing a file, a ``data_sources`` text pipeline);
+they are loaded from disk as golden inputs, next to the inline definitions below.
 """
 import json
 import os
@@ -16,8 +17,7 @@ from aiko_services_amd.pipeline.definition import (DefinitionError, parse_pipeli
                                                    parse_pipeline_definition_dict)
 from aiko_services_amd.runtime import event
 
-REF = Path("/root/reference/src/aiko_services")
-needs_ref = pytest.mark.skipif(not REF.exists(), reason="reference checkout not present")
+GOLDEN = Path(__file__).resolve().parent / "golden" / "definitions"
 
 
 @pytest.fixture(scope="module")
@@ -271,17 +271,15 @@ def test_process_frame_over_message_bus(aiko_process):
     assert cmd == "process_frame" and info["frame_id"] == "4" and data["f"] == "6"
 
 
-@needs_ref
 @pytest.mark.parametrize("name", ["pipeline_local.json", "pipeline_paths.json", "pipeline_example.json"])
 def test_reference_definitions_parse(name):
-    d = parse_pipeline_definition(str(REF / "examples" / "pipeline" / name))
+    d = parse_pipeline_definition(str(GOLDEN / name))
     assert d.elements
 
 
-@needs_ref
 def test_reference_pipeline_local_runs(aiko_process, tmp_path, monkeypatch):
     monkeypatch.chdir(tmp_path)   # PE_Inspect writes z_inspect.txt in cwd
-    path = REF / "examples" / "pipeline" / "pipeline_local.json"
+    path = GOLDEN / "pipeline_local.json"
     d = parse_pipeline_definition(str(path))
     pipeline, q = _create(d, stream_id="r1", pathname=str(path))
     pipeline.create_frame({"stream_id": "r1", "frame_id": 0}, {"b": 0})
@@ -290,9 +288,8 @@ def test_reference_pipeline_local_runs(aiko_process, tmp_path, monkeypatch):
     assert (tmp_path / "z_inspect.txt").exists()
 
 
-@needs_ref
 def test_reference_text_pipeline_runs(aiko_process, tmp_path, monkeypatch):
-    media = REF / "elements" / "media"
+    media = GOLDEN
     (tmp_path / "data_in").symlink_to(media / "data_in")
     (tmp_path / "data_out").mkdir()
     monkeypatch.chdir(tmp_path)
