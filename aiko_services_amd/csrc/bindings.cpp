@@ -60,6 +60,8 @@ int aiko_conv3x3_patch(const void* x, const void* wimg, const float* bias, void*
 int aiko_bneck_fused(const void* x, const void* w1, const float* b1, const void* w2, const float* b2,
                      const void* w3, const float* b3, void* y, int B, int H, int W, int cin, int grid,
                      unsigned* dbg, hipStream_t stream);
+int aiko_conv3x3_exp(const void* t1, const void* w2, const float* b2, const void* w3img, const float* b3,
+                     const void* res, void* y, int B, int H, int W, int N, int grid, hipStream_t stream);
 int aiko_conv_chain(const void* A, const void* W1, const float* b1, const void* R, void* Y, const void* W2,
                     const float* b2, void* Z, const void* A2, int M, int K1, int N1, int N2, int grid,
                     hipStream_t stream);
@@ -693,6 +695,40 @@ void bneck_fused_out(const at::Tensor& x, const at::Tensor& w1, const at::Tensor
                                 w3.data_ptr(), b3.data_ptr<float>(), y.data_ptr(), (int)B, (int)H, (int)W, (int)cin,
                                 (int)grid, dbg_ptr, cur_stream()),
                "bneck_fused");
+}
+
+// A bottleneck's 3x3 conv + 1x1 expansion + identity residual + ReLU in one launch
+// (conv_exp.hip): t1 [B, H, W, 256] -> y [B, H, W, N], N % 256 == 0; w2 [256, 2304] (3x3,
+// tap-major); w3 the MFMA fragment image of the [N, 256] expansion weight
+// (ops.conv.exp_weight: [N / 16, 8, 64, 8]); res [B, H, W, N].  grid: workgroups (0: one per
+// 256-pixel tile).  Allocates nothing and does not synchronise.
+void conv3x3_exp_out(const at::Tensor& t1, const at::Tensor& w2, const at::Tensor& b2, const at::Tensor& w3,
+                     const at::Tensor& b3, const at::Tensor& res, at::Tensor& y, int64_t grid) {
+  for (const at::Tensor* t : {&t1, &w2, &b2, &w3, &b3, &res, (const at::Tensor*)&y}) {
+    check_cuda(*t, "conv3x3_exp operand");
+    TORCH_CHECK(t->is_contiguous() && reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "aiko.conv3x3_exp_out: operands must be contiguous and 16-byte aligned");
+  }
+  for (const at::Tensor* t : {&t1, &w2, &w3, &res, (const at::Tensor*)&y})
+    TORCH_CHECK(t->scalar_type() == at::kBFloat16, "aiko.conv3x3_exp_out: bf16 activations / weights");
+  for (const at::Tensor* t : {&b2, &b3})
+    TORCH_CHECK(t->scalar_type() == at::kFloat, "aiko.conv3x3_exp_out: fp32 biases");
+  TORCH_CHECK(t1.dim() == 4 && t1.size(3) == 256, "aiko.conv3x3_exp_out: t1 must be [B, H, W, 256] NHWC");
+  const int64_t B = t1.size(0), H = t1.size(1), W = t1.size(2);
+  TORCH_CHECK(y.dim() == 4 && y.size(0) == B && y.size(1) == H && y.size(2) == W, "aiko.conv3x3_exp_out: y must be [B, H, W, N]");
+  const int64_t N = y.size(3);
+  TORCH_CHECK(N > 0 && N % 256 == 0, "aiko.conv3x3_exp_out: N must be a multiple of 256");
+  TORCH_CHECK(res.sizes() == y.sizes(), "aiko.conv3x3_exp_out: res must have y's shape (identity residual)");
+  TORCH_CHECK(w2.numel() == 256 * 9 * 256 && w2.size(0) == 256, "aiko.conv3x3_exp_out: w2 [256, 2304] (3x3, tap-major)");
+  TORCH_CHECK(w3.numel() == N * 256, "aiko.conv3x3_exp_out: w3 must be the [N / 16, 8, 64, 8] fragment image");
+  TORCH_CHECK(b2.numel() == 256 && b3.numel() == N, "aiko.conv3x3_exp_out: biases [256], [N]");
+  TORCH_CHECK(y.data_ptr() != res.data_ptr() && y.data_ptr() != t1.data_ptr(), "aiko.conv3x3_exp_out: in place is not supported");
+  TORCH_CHECK(grid >= 0, "aiko.conv3x3_exp_out: grid must be >= 0 (0: one workgroup per tile)");
+  TORCH_CHECK(B > 0 && H > 0 && W > 0 && B * H * W * N * 2 < 0x7ffffff0LL,
+              "aiko.conv3x3_exp_out: tensors too large for 32-bit offsets");
+  check_launch(aiko_conv3x3_exp(t1.data_ptr(), w2.data_ptr(), b2.data_ptr<float>(), w3.data_ptr(), b3.data_ptr<float>(),
+                                res.data_ptr(), y.data_ptr(), (int)B, (int)H, (int)W, (int)N, (int)grid, cur_stream()),
+               "conv3x3_exp");
 }
 
 // uint8 frames -> letterbox/normalise -> k x k stem conv (+bias, act) -> bf16 NHWC ``out``
@@ -1437,6 +1473,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("conv3x3_rows_out(Tensor x, Tensor wimg, Tensor? bias, Tensor? res, Tensor(a!) y, int act, int grid=0) -> ()");
   m.def("conv_chain_out(Tensor A, Tensor W1, Tensor b1, Tensor? R, Tensor(a!) Y, Tensor W2, Tensor b2, Tensor(b!) Z, int grid=0, Tensor? A2=None) -> ()");
   m.def("bneck_fused_out(Tensor x, Tensor w1, Tensor b1, Tensor w2, Tensor b2, Tensor w3, Tensor b3, Tensor(a!) y, int grid=0, Tensor? dbg=None) -> ()");
+  m.def("conv3x3_exp_out(Tensor t1, Tensor w2, Tensor b2, Tensor w3, Tensor b3, Tensor res, Tensor(a!) y, int grid=0) -> ()");
   m.def("maxpool_out(Tensor x, Tensor(a!) y, int k, int s, int p) -> ()");
   m.def("avgpool_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("mean_rows_out(Tensor x, Tensor(a!) y) -> ()");
@@ -1467,6 +1504,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("maxpool_out", &maxpool_out);
   m.impl("conv_chain_out", &conv_chain_out);
   m.impl("bneck_fused_out", &bneck_fused_out);
+  m.impl("conv3x3_exp_out", &conv3x3_exp_out);
   m.impl("conv3x3_patch_out", &conv3x3_patch_out);
   m.impl("conv3x3_patchw_out", &conv3x3_patchw_out);
   m.impl("conv3x3_rows_out", &conv3x3_rows_out);

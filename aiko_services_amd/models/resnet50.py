@@ -108,6 +108,9 @@ class ResNet50(WeightsMixin):
         self.chain = os.environ.get("AIKO_RESNET_CHAIN", "1") != "0"
         # stage-1 bottlenecks as ONE launch each (bneck_fused.hip: t1 / t2 stay in LDS)
         self.bneck = os.environ.get("AIKO_RESNET_BNECK", "1") != "0"
+        # stage-3 identity blocks: 3x3 conv + 1x1 expansion + residual as ONE launch
+        # (conv_exp.hip: t2 stays in LDS)
+        self.exp3 = os.environ.get("AIKO_RESNET_EXP", "1") != "0"
         # uint8 frames of the model's own size go straight into the fused stem (it normalises
         # while filling its LDS patch): no pre-processing kernel, no bf16 stem buffer
         self.stem_u8 = os.environ.get("AIKO_STEM_U8", "1") != "0"
@@ -224,10 +227,15 @@ class ResNet50(WeightsMixin):
         if t1 is None:
             t1 = C.conv2d(x, blk.conv1, out=self._buf(tag + "t1", (B, H, W, blk.conv1.cout))[sl])
         Ho, Wo = blk.conv2.out_hw(H, W)
-        t2 = C.conv2d(t1, blk.conv2, out=self._buf(tag + "t2", (B, Ho, Wo, blk.conv2.cout))[sl])
         key = "xa" if bi % 2 == 0 else "xb"
-        out = self._buf(tag + key, (B, Ho, Wo, blk.conv3.cout))[sl]
         nxt = self.blocks[bi + 1] if bi + 1 < len(self.blocks) else None
+        if (self.exp3 and blk.down is None and C.conv_exp_ok(blk.conv2, blk.conv3, t1, x)
+                and not (chain and self.chain and nxt is not None and C.chain_ok(blk.conv3, nxt.conv1))):
+            out = self._buf(tag + key, (B, Ho, Wo, blk.conv3.cout))[sl]
+            if out.is_contiguous():
+                return C.conv3x3_exp(t1, blk.conv2, blk.conv3, x, out=out), None
+        t2 = C.conv2d(t1, blk.conv2, out=self._buf(tag + "t2", (B, Ho, Wo, blk.conv2.cout))[sl])
+        out = self._buf(tag + key, (B, Ho, Wo, blk.conv3.cout))[sl]
         if blk.fused is not None and self.fuse_shortcut:
             if (chain and self.chain and nxt is not None and C.chain_dual_ok(blk.fused, nxt.conv1)
                     and (ch * Ho * Wo) % 64 == 0 and x.is_contiguous() and (H, W) == (Ho, Wo)):

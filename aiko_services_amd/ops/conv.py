@@ -384,9 +384,10 @@ def patchw_weight(spec: ConvSpec) -> torch.Tensor:
 
 def refresh_derived(spec: ConvSpec) -> None:
     """Re-derive, in place, every lazily built weight image this spec already holds (patch /
-    patchw / rows kernels).  Called by ``models.weights.load_state_dict``: a captured hipGraph
+    patchw / rows / conv3x3_exp kernels).  Called by ``models.weights.load_state_dict``: a captured hipGraph
     replays these images without re-entering Python, so they cannot wait for the next eager call."""
-    for attr, derive in (("_patch_w", patch_weight), ("_patchw_w", patchw_weight), ("_rows_w", rows_weight)):
+    for attr, derive in (("_patch_w", patch_weight), ("_patchw_w", patchw_weight), ("_rows_w", rows_weight),
+                         ("_exp_w", exp_weight)):
         if getattr(spec, attr, None) is not None:
             derive(spec)
 
@@ -841,6 +842,62 @@ def bneck_fused(x: torch.Tensor, conv1: ConvSpec, conv2: ConvSpec, conv3: ConvSp
         out = torch.empty(*x.shape[:3], 256, dtype=torch.bfloat16, device=x.device)
     torch.ops.aiko.bneck_fused_out(x, conv1.weight, conv1.bias, conv2.weight, conv2.bias, conv3.weight,
                                    conv3.bias, out, grid)
+    return out
+
+
+def conv_exp_ok(spec2: ConvSpec, spec3: ConvSpec, t1: torch.Tensor, residual: torch.Tensor | None) -> bool:
+    """Can ``spec2`` (3x3 / stride 1 / pad 1, 256 -> 256) and the following ``spec3`` (1x1
+    256 -> N, N a multiple of 256, identity residual) run as ONE ``conv3x3_exp`` launch
+    (``conv_exp.hip``)?  Both with a bias and ReLU; ``t1`` [B, H, W, 256] and ``residual``
+    [B, H, W, N] contiguous bf16 NHWC, any H and W."""
+    def relu_bias(s):
+        return s.kind == "conv" and s.bias is not None and s.act == ACT_RELU and s.K1 is None
+    if not (relu_bias(spec2) and relu_bias(spec3) and residual is not None):
+        return False
+    n = spec3.cout
+    return (spec2.R == 3 and spec2.S == 3 and spec2.stride == 1 and spec2.pad == 1 and spec2.Cc == 256
+            and spec2.cout == 256 and tuple(spec2.weight.shape) == (256, 2304)
+            and spec3.R == 1 and spec3.S == 1 and spec3.stride == 1 and spec3.pad == 0 and spec3.Cc == 256
+            and tuple(spec3.weight.shape) == (n, 256) and n % 256 == 0
+            and t1.dim() == 4 and t1.shape[3] == 256 and t1.dtype == torch.bfloat16 and t1.is_contiguous()
+            and residual.dtype == torch.bfloat16 and residual.is_contiguous()
+            and tuple(residual.shape) == (*t1.shape[:3], n) and residual.numel() * 2 < 0x7ffffff0)
+
+
+def exp_weight(spec: ConvSpec) -> torch.Tensor:
+    """[N / 16, 8, 64, 8] MFMA fragment image of a 1x1 256 -> N weight for conv_exp.hip:
+    (16-output-channel block, 32-deep K slice, lane = 16 (k group) + output row, 8 channels) —
+    each (block, slice) is the contiguous 1 KB one wave loads straight into registers.  Cached
+    on the spec and re-derived in place when the weight changes (as patchw_weight)."""
+    key = (spec.weight.data_ptr(), spec.weight._version)
+    cached = getattr(spec, "_exp_w", None)
+    if cached is not None and cached[0] == key:
+        return cached[1]
+    n = spec.weight.shape[0]
+    w = spec.weight.view(n // 16, 16, 8, 4, 8)               # [nb, fr, ks, fq, e]
+    img = w.permute(0, 2, 3, 1, 4).reshape(n // 16, 8, 64, 8)
+    if cached is not None:
+        cached[1].copy_(img)
+        img = cached[1]
+    else:
+        img = img.contiguous()
+    spec._exp_w = (key, img)
+    return img
+
+
+def conv3x3_exp(t1: torch.Tensor, spec2: ConvSpec, spec3: ConvSpec, residual: torch.Tensor,
+                out: torch.Tensor | None = None, grid: int = 0) -> torch.Tensor:
+    """``relu(conv1x1(relu(conv3x3(t1, spec2)), spec3) + residual)`` in one kernel
+    (``conv_exp.hip``): the 256-channel intermediate is rounded to bf16 as the unfused path
+    rounds it, but stays in LDS.  ``grid`` workgroups (0 = one per 256-pixel tile).  See
+    :func:`conv_exp_ok`."""
+    if not conv_exp_ok(spec2, spec3, t1, residual):
+        raise ValueError("conv3x3_exp: shapes not eligible (see conv_exp_ok)")
+    if out is None:
+        out = torch.empty_like(residual)
+    elif not (out.is_contiguous() and out.shape == residual.shape and out.dtype == torch.bfloat16):
+        raise ValueError("conv3x3_exp: out must be contiguous bf16 with the residual's shape")
+    torch.ops.aiko.conv3x3_exp_out(t1, spec2.weight, spec2.bias, exp_weight(spec3), spec3.bias, residual, out, grid)
     return out
 
 
