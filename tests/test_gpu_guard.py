@@ -1,0 +1,1279 @@
+"""Guard-band and poison runs of the conv and vision kernels (run on MI355X: -m gpu).
+
+Every case builds its inputs once on the CPU from a seeded generator and runs the kernel twice:
+*plain*, on fresh tensors as the other test files do, and *guarded*, with every tensor the
+binding receives (inputs, second source, residual, outputs, weights, biases, scratch, zero page)
+a view from ``kernel_guard.guarded`` holding the same values between two NaN guards.  Then, in
+this order:
+
+1. every guard is bit-identical to its saved copy — nothing outside any tensor was written;
+2. the guarded output is finite everywhere — no poison was consumed, every element was written;
+3. the guarded output is bit-identical to the plain output — the kernels use no atomics and the
+   tile is forced, so where the operands live must not change one bit;
+4. the plain output meets the bound of the kernel's existing test, unchanged.
+
+Each kernel family has a case whose last tile is partial; the case computes the split its
+launcher makes — ``M % BM`` for the tiled convs, the row split of the row-stream kernels, the
+element count over the 256-thread block (or the rows over the waves of a block) of the pointwise
+ops — and asserts it is non-zero, so a case that stops exercising a tail fails loudly.  Two
+families cannot have a partial tile: conv_chain's launcher refuses M % 64 != 0 and the C2f
+launchers (c2f_fused.hip) refuse H % rb != 0.  The conv_chain cases assert an uneven walk of the
+persistent grid instead (3 tiles over 2 workgroups); the C2f kernels are not persistent (one
+workgroup per band of rb rows), so their cases run every band height of the existing tests:
+several bands with halo rows recomputed at band edges, and rb == H, the single band with zero
+rows on both sides.
+
+NaN cannot show an out-of-tensor tap of a max-reduction (``fmaxf`` drops it), so the max-pool
+cases run a second time with +3e38 in the guards and gap channels: it would win every maximum.
+"""
+import dataclasses
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from kernel_guard import GuardError, guarded
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+BF16 = torch.bfloat16
+NAN = float("nan")
+
+
+def _rel_err(a, b):
+    a, b = a.float(), b.float()
+    return ((a - b).norm() / (b.norm() + 1e-12)).item()
+
+
+def _nhwc(x_nchw):
+    return x_nchw.permute(0, 2, 3, 1).contiguous()
+
+
+def _nchw(x_nhwc):
+    return x_nhwc.permute(0, 3, 1, 2)
+
+
+def _bits(t):
+    t = t.contiguous()
+    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+class Operands:
+    """Tensor factory of one run: plain (fresh tensors) or guarded (views between NaN guards)."""
+
+    def __init__(self, on: bool, poison=None):
+        self.on, self.checks, self.poison = on, [], poison
+
+    @property
+    def gap(self):
+        """What the gap channels of a sliced input hold: zero (plain) or the poison (guarded)."""
+        return 0.0 if not self.on else NAN if self.poison is None else self.poison
+
+    def _guard(self, shape, dtype, values, name):
+        view, check = guarded(shape, dtype, DEV, values=values, name=name,
+                              poison=self.poison if dtype.is_floating_point else None)
+        self.checks.append(check)
+        return view
+
+    def inp(self, values, name="input"):
+        """An input holding ``values`` (CPU or device tensor)."""
+        if not self.on:
+            return values.to(DEV).contiguous().clone()
+        return self._guard(values.shape, values.dtype, values.to(DEV), name)
+
+    def inp_slice(self, values, pitch, c0, name="input slice"):
+        """``values`` [..., C] as channels [c0, c0 + C) of a [..., pitch] buffer (ld > C).  The
+        gap channels are zero in the plain run (as the other test files have them) and poison in
+        the guarded run."""
+        C = values.shape[-1]
+        wide = torch.full((*values.shape[:-1], pitch), self.gap, dtype=values.dtype)
+        wide[..., c0:c0 + C] = values
+        return self.inp(wide, name)[..., c0:c0 + C]
+
+    def out(self, shape, dtype=BF16, name="output"):
+        """An output: NaN (floating point) in both runs, so an unwritten element is non-finite."""
+        if not self.on:
+            return torch.full(shape, NAN, dtype=dtype, device=DEV) if dtype.is_floating_point else \
+                torch.zeros(shape, dtype=dtype, device=DEV)
+        return self._guard(shape, dtype, None, name)
+
+    def spec(self, spec, name="spec"):
+        """``spec`` with its weight and bias swapped for guarded copies: a NEW ConvSpec, so every
+        derived image (patch / patchw / rows / exp / stem images) is re-derived from them."""
+        if not self.on:
+            return dataclasses.replace(spec)
+        return dataclasses.replace(spec, weight=self.inp(spec.weight, name + ".weight"),
+                                   bias=None if spec.bias is None else self.inp(spec.bias, name + ".bias"))
+
+    def check(self):
+        for c in self.checks:
+            c()
+
+
+def run_both(case, poison=None):
+    """``case(ops) -> tensor | tuple of tensors``: run plain and guarded, assert 1-3, return the
+    plain outputs (for assertion 4, the caller's).  ``poison``: a finite value instead of NaN in
+    the guards and gap channels (max-reductions)."""
+    plain_ops = Operands(False)
+    plain = case(plain_ops)
+    torch.cuda.synchronize()
+    ops = Operands(True, poison)
+    from aiko_services_amd.ops import conv as C
+    saved = dict(C._ZERO)                   # the LDS-DMA kernels' zero page is an operand too
+    try:
+        dev = torch.device(DEV, torch.cuda.current_device())
+        C._ZERO[dev] = ops.inp(torch.zeros(32, dtype=BF16), "zero page")
+        guard = case(ops)
+        torch.cuda.synchronize()
+    finally:
+        C._ZERO.clear()
+        C._ZERO.update(saved)
+    single = not isinstance(plain, (tuple, list))
+    plain, guard = ((plain,), (guard,)) if single else (tuple(plain), tuple(guard))
+    assert ops.checks, "the guarded run allocated no guarded tensor"
+    ops.check()                                                                   # 1
+    for i, t in enumerate(guard):                                                 # 2
+        if t.dtype.is_floating_point:
+            bad = (~torch.isfinite(t.float())).sum().item()
+            assert bad == 0, f"guarded output {i}: {bad} non-finite element(s) (poison consumed or unwritten)"
+    for i, (p, t) in enumerate(zip(plain, guard)):                                # 3
+        if not torch.equal(_bits(p), _bits(t)):
+            n = (_bits(p) != _bits(t)).sum().item()
+            raise AssertionError(f"output {i}: {n} element(s) differ between the plain and the guarded run")
+    return plain[0] if single else plain
+
+
+# ---- the helper on the device --------------------------------------------------------------------
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float32, torch.uint8])
+@pytest.mark.parametrize("side,offset", [("before", -1), ("after", 0)])
+def test_guard_reports_device_write(dtype, side, offset):
+    vals = torch.ones(2, 5, 7, 16)
+    view, check = guarded(vals.shape, dtype, DEV, values=vals)
+    assert view.is_cuda and view.is_contiguous() and view.storage_offset() > 0 and view.data_ptr() % 256 == 0
+    check()
+    at = check.start + offset if side == "before" else check.start + check.numel + offset
+    check.flat[at:at + 1] = 3
+    with pytest.raises(GuardError) as e:
+        check()
+    assert e.value.side == side and e.value.offset == offset
+
+
+@pytest.mark.parametrize("side", ["before", "after"])
+def test_guard_poison_is_live(side):
+    """One row of guard inside a 3x3 conv's input makes the output non-finite: a kernel that
+    reads a tap outside its tensor cannot pass assertion 2."""
+    g = torch.Generator().manual_seed(1)
+    H, W, C = 6, 5, 8
+    x, check = guarded((1, H, W, C), torch.float32, DEV, values=torch.randn(1, H, W, C, generator=g))
+    w = torch.randn(4, C, 3, 3, generator=g).to(DEV)
+    assert torch.isfinite(F.conv2d(_nchw(x), w, padding=1)).all()
+    s = check.start - W * C if side == "before" else check.start
+    ext = check.flat[s:s + (H + 1) * W * C].view(1, H + 1, W, C)
+    assert not torch.isfinite(F.conv2d(_nchw(ext), w, padding=1)).all()
+    check()
+
+
+# ---- conv2d: every tiled variant -----------------------------------------------------------------
+
+_G13 = (1, 13, 9, 192, 72, 3, 2, 1, "gelu", True)
+_S200 = (1, 9, 11, 128, 200, 3, 1, 1, "silu", True)
+_N7 = (1, 9, 10, 16, 32, 3, 1, 1, "gelu", True)
+_PW = (3, 14, 14, 256, 1024, 1, 1, 0, None, True)
+_G13x3 = (3,) + _G13[1:]
+
+CONV_CASES = [
+    # variants 0 / 1: register-staged and LDS-DMA igemm (N tail Cout = 24; exact-N 80)
+    ((1, 9, 11, 40, 24, 3, 1, 1, None, False), (64, 64), 0),
+    ((1, 9, 11, 40, 24, 3, 1, 1, None, False), (64, 64, 1), 0),
+    ((1, 13, 17, 80, 80, 1, 1, 0, None, True), (128, 80, 1), 0),
+    # variants 2 / 3 / 5 / 6: buffer-DMA kernels
+    (_G13, (128, 64, 2), 0),
+    ((1, 9, 11, 128, 64, 3, 1, 1, "silu", False), (64, 64, 3), 0),
+    ((1, 9, 11, 128, 64, 3, 2, 1, "silu", False), (256, 128, 5), 0),
+    ((1, 9, 11, 128, 256, 3, 2, 1, "silu", True), (128, 256, 6), 0),
+    # variants 4 / 20: persistent walks, 3 workgroups; B = 3: several tiles, ending on the tail
+    (_G13, (64, 64, 4), 3), (_G13, (256, 128, 20), 3),
+    (_G13x3, (64, 64, 4), 3), (_G13x3, (256, 128, 20), 3),
+    # ... B = 24: four 256-row tiles over 3 workgroups, workgroup 0 walks tiles 0 and 3 (the
+    # tail); with and without a residual (3- and 2-slot forms)
+    ((24,) + _G13[1:], (256, 128, 20), 3), ((24,) + _G13[1:9] + (False,), (256, 256, 20), 3),
+    # variant 4 sizes its grid from the CU count alone (2 workgroups per CU): 264 x 2 tiles of
+    # 64 x 64 are more than 512 slots, so every workgroup walks two tiles and the last one ends
+    # on the 43-row tail — the only multi-tile walk of this kernel in the suite
+    ((3, 75, 75, 64, 72, 3, 1, 1, "gelu", True), (64, 64, 4), -1),
+    # variants 8 / 9 / 11 / 19: conv_wide (N tail Cout = 200 / 72)
+    (_S200, (256, 128, 8), 0), (_S200, (256, 128, 11), 0), (_S200, (128, 256, 19), 0),
+    (_G13, (64, 128, 9), 0), (_G13, (128, 128, 19), 0),
+    # variant 18: exact-N conv_wide
+    ((2, 9, 13, 128, 144, 3, 1, 1, "silu", True), (128, 144, 18), 0),
+    ((1, 17, 19, 64, 160, 3, 1, 1, "relu", True), (256, 80, 18), 0),
+    # variant 7: direct narrow kernel (tiles of 8 / 16 rows x 32 columns)
+    (_N7, (8, 32, 7), 0), (_N7, (16, 32, 7), 0),
+    ((1, 9, 10, 32, 32, 3, 1, 1, "gelu", True), (16, 64, 7), 0),
+    ((1, 33, 65, 16, 32, 3, 2, 1, "silu", False), (8, 32, 7), 0),
+    # variants 12 / 13 / 14: persistent pointwise kernels
+    (_PW, (128, 128, 12), 0), (_PW, (64, 128, 13), 0), (_PW, (64, 128, 14), 0),
+    ((1, 7, 7, 512, 2048, 1, 1, 0, "relu", True), (64, 128, 13), 0),
+    ((1, 7, 7, 128, 512, 1, 1, 0, "relu", True), (64, 128, 13), 0),
+    # ... with more M tiles than workgroups per channel block (CUs / (Cout / BN) of them, from
+    # the CU count alone), so some workgroup walks several tiles and ends on the tail: K = 256
+    # (BN 128), K = 512 (BN 64), K = 128 (BN 256)
+    ((11, 14, 14, 256, 2048, 1, 1, 0, "relu", True), (128, 128, 12), -2),
+    ((11, 14, 14, 256, 2048, 1, 1, 0, "relu", True), (64, 128, 13), -2),
+    ((11, 14, 14, 256, 2048, 1, 1, 0, "relu", True), (64, 128, 14), -2),
+    ((12, 7, 7, 512, 2048, 1, 1, 0, "relu", True), (64, 128, 13), -2),
+    ((3, 28, 28, 128, 2048, 1, 1, 0, "silu", False), (64, 128, 13), -2),
+]
+_PW_BN = {128: 256, 256: 128, 512: 64}          # variant 13 / 14 channel block per K
+
+
+def _conv_id(p):
+    shape, tile, grid = p
+    v = tile[2] if len(tile) > 2 else 0
+    return f"v{v}-{'x'.join(str(s) for s in shape[:5])}-k{shape[5]}s{shape[6]}-t{tile[0]}x{tile[1]}" + \
+        (f"-g{grid}" if grid > 0 else "-multi" if grid < 0 else "")
+
+
+@pytest.mark.parametrize("shape,tile,grid", CONV_CASES, ids=[_conv_id(p) for p in CONV_CASES])
+def test_conv2d_guarded(native, monkeypatch, shape, tile, grid):
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    B, H, W, cin, cout, k, stride, pad, act, res = shape
+    variant = tile[2] if len(tile) > 2 else 0
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    if grid > 0:
+        monkeypatch.setenv("AIKO_CONV_PERS_GRID", str(grid))
+    g = torch.Generator().manual_seed(1234)
+    w = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
+    b = torch.randn(cout, generator=g) * 0.1
+    spec0 = C.make_conv_spec(w, b, stride=stride, pad=pad, act=act, device=DEV)
+    x = torch.randn(B, cin, H, W, generator=g).to(BF16)
+    x_nhwc = torch.zeros(B, H, W, spec0.Cc, dtype=BF16)
+    x_nhwc[..., :cin] = _nhwc(x)
+    Ho, Wo = spec0.out_hw(H, W)
+    r = torch.randn(B, cout, Ho, Wo, generator=g).to(BF16) if res else None
+    M = B * Ho * Wo
+    if variant == 7:
+        assert Ho % tile[0] != 0 or Wo % 32 != 0, "case has no partial tile"
+    else:
+        assert M % tile[0] != 0, "case has no partial last M tile"
+    mtiles = -(-M // tile[0])
+    if grid == -1:                                          # variant 4: 2 workgroup slots per CU
+        assert variant == 4 and mtiles * -(-cout // tile[1]) > 2 * cus, "one tile per workgroup"
+    elif grid == -2:                                        # conv_pw: CUs / channel blocks groups per block
+        bn = 128 if variant == 12 else _PW_BN[spec0.K]
+        assert cout % bn == 0 and mtiles > max(1, cus // (cout // bn)), "one tile per workgroup"
+    elif B == 24:
+        assert mtiles * -(-cout // tile[1]) > grid, "one tile per workgroup"
+
+    def case(ops):
+        out = ops.out((B, Ho, Wo, cout))
+        C.conv2d(ops.inp(x_nhwc, "x"), ops.spec(spec0), residual=None if r is None else ops.inp(_nhwc(r), "residual"),
+                 out=out, tile=tile)
+        return out
+
+    y = run_both(case)
+    ref = R.conv_ref(x.float().to(DEV), spec0, None if r is None else r.float().to(DEV))
+    err = _rel_err(_nchw(y), ref)
+    assert err < 1e-2, err
+
+
+@pytest.mark.parametrize("cin,cout,k,tile,pitch,c0", [
+    (32, 64, 3, (64, 64), 96, 0), (32, 64, 3, (64, 64), 96, 32), (32, 64, 3, (64, 64, 1), 96, 32),
+    (40, 24, 3, (64, 64, 1), 64, 8), (16, 16, 3, (8, 32, 7), 48, 16), (32, 32, 3, (16, 64, 7), 96, 32),
+    (128, 64, 3, (64, 64, 2), 192, 64), (128, 64, 3, (64, 64, 4), 192, 64), (128, 200, 3, (256, 128, 8), 192, 64),
+    (128, 144, 3, (128, 144, 18), 192, 32), (256, 256, 1, (128, 128, 12), 384, 64),
+    (256, 256, 1, (64, 128, 13), 384, 64), (128, 256, 1, (64, 128, 13), 384, 64)])
+def test_conv2d_channel_slices_guarded(native, cin, cout, k, tile, pitch, c0):
+    """Input and residual from channel slices (pitch > Cc: the gap channels are poison, so a K
+    block that runs past its tap's channels shows), output into a slice of a NaN concat buffer
+    whose other channels must stay NaN — in rows 0 and M-1 too.  M = 198: a partial last tile."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    g = torch.Generator().manual_seed(7)
+    B, H, W = 2, 9, 11
+    x = torch.randn(B, H, W, cin, generator=g).to(BF16)
+    r = torch.randn(B, H, W, cout, generator=g).to(BF16)
+    spec0 = C.make_conv_spec(torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5,
+                             torch.randn(cout, generator=g) * 0.1, pad=k // 2, act="silu", device=DEV)
+    assert spec0.Cc == cin and (B * H * W) % tile[0] != 0 and H % tile[0] != 0
+    ro = 8 * ((cout + 7) // 8)
+
+    def case(ops):
+        cat = ops.out((B, H, W, 32 + cout + 16), name="concat buffer")
+        C.conv2d(ops.inp_slice(x, pitch, c0, "x"), ops.spec(spec0), residual=ops.inp_slice(r, ro + 24, 16, "residual"),
+                 out=cat[..., 32:32 + cout], tile=tile, residual_after_act=True)
+        torch.cuda.synchronize()
+        assert torch.isnan(cat[..., :32].float()).all() and torch.isnan(cat[..., 32 + cout:].float()).all(), \
+            "wrote outside the output's channel slice"
+        return cat[..., 32:32 + cout]
+
+    y = run_both(case)
+    ref = R.conv_ref(_nchw(x).float().to(DEV), spec0, _nchw(r).float().to(DEV), residual_after_act=True)
+    assert _rel_err(_nchw(y), ref) < 1e-2
+
+
+@pytest.mark.parametrize("B,H,cout,stride", [(1, 18, 384, 2), (2, 18, 384, 2), (13, 18, 2048, 2)])
+def test_conv_pw_dual_guarded(native, B, H, cout, stride):
+    """Variant 13 with a second source (Ho = 9, M = 81 / 162: 64-pixel tiles end in a tail;
+    B = 13, Cout = 2048: 17 tiles over 16 workgroups per channel block, one walks two)."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    g = torch.Generator().manual_seed(B * 100 + H + cout)
+    Ho = (H - 1) // stride + 1
+    main = C.make_conv_spec(torch.randn(cout, 128, 1, 1, generator=g) / 128 ** 0.5, torch.randn(cout, generator=g),
+                            act="relu", device=DEV)
+    down = C.make_conv_spec(torch.randn(cout, 256, 1, 1, generator=g) / 256 ** 0.5, torch.randn(cout, generator=g),
+                            stride=stride, device=DEV)
+    fused = C.fuse_shortcut(main, down)
+    t = torch.randn(B, Ho, Ho, 128, generator=g).to(BF16)
+    x = torch.randn(B, H, H, 256, generator=g).to(BF16)
+    assert (B * Ho * Ho) % 64 != 0
+    if cout == 2048:
+        cus = torch.cuda.get_device_properties(0).multi_processor_count
+        assert -(-B * Ho * Ho // 64) > max(1, cus // (cout // 128)), "one tile per workgroup"
+
+    def case(ops):
+        out = ops.out((B, Ho, Ho, cout))
+        C.conv2d(ops.inp(t, "t"), ops.spec(fused), x2=ops.inp(x, "x2"), out=out, tile=(64, 128, 13))
+        return out
+
+    y = run_both(case)
+    idn = R.conv_ref(_nchw(x).float().to(DEV), down)
+    ref = R.conv_ref(_nchw(t).float().to(DEV), main, idn)
+    assert _rel_err(_nchw(y), ref) < 1e-2
+
+
+@pytest.mark.parametrize("variant,grid", [(0, 0), (2, 0), (8, 0), (20, 5)])
+def test_fused_projection_guarded(native, monkeypatch, variant, grid):
+    """conv3(t) + down(x) as one K-concatenated igemm with two A sources, M = 49."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    if grid:
+        monkeypatch.setenv("AIKO_CONV_PERS_GRID", str(grid))
+    B, H, cin_main, cin_sc, cout, stride = 1, 14, 512, 1024, 2048, 2
+    g = torch.Generator().manual_seed(21)
+    Ho = H // stride
+    main = C.make_conv_spec(torch.randn(cout, cin_main, 1, 1, generator=g) / cin_main ** 0.5,
+                            torch.randn(cout, generator=g), act="relu", device=DEV)
+    down = C.make_conv_spec(torch.randn(cout, cin_sc, 1, 1, generator=g) / cin_sc ** 0.5,
+                            torch.randn(cout, generator=g), stride=stride, device=DEV)
+    fused = C.fuse_shortcut(main, down)
+    t = torch.randn(B, Ho, Ho, cin_main, generator=g).to(BF16)
+    x = torch.randn(B, H, H, cin_sc, generator=g).to(BF16)
+    tile = (256, 128, variant) if variant in (8, 20) else (64, 128, variant)
+    assert (B * Ho * Ho) % tile[0] != 0
+
+    def case(ops):
+        out = ops.out((B, Ho, Ho, cout))
+        C.conv2d(ops.inp(t, "t"), ops.spec(fused), x2=ops.inp(x, "x2"), out=out, tile=tile)
+        return out
+
+    y = run_both(case)
+    idn = R.conv_ref(_nchw(x).float().to(DEV), down)
+    ref = R.conv_ref(_nchw(t).float().to(DEV), main, idn)
+    assert _rel_err(_nchw(y), ref) < 1e-2
+
+
+# ---- patch / patchw / rows kernels ---------------------------------------------------------------
+
+@pytest.mark.parametrize("B,H,W,act", [(3, 1, 24, "relu"), (3, 13, 24, "silu")])
+def test_conv3x3_patch_guarded(native, B, H, W, act):
+    """Variant 10: 8-row tiles, H = 1 / 13: every image ends in a partial tile."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    g = torch.Generator().manual_seed(B * 100 + H)
+    spec0 = C.make_conv_spec(torch.randn(64, 64, 3, 3, generator=g) / 24, torch.randn(64, generator=g) * 0.1,
+                             pad=1, act=act, device=DEV)
+    x = torch.randn(B, 64, H, W, generator=g).to(BF16)
+    assert H % 8 != 0
+
+    def case(ops):
+        out = ops.out((B, H, W, 64))
+        C.conv2d(ops.inp(_nhwc(x), "x"), ops.spec(spec0), out=out, tile=(8, 64, 10))
+        return out
+
+    y = run_both(case)
+    assert _rel_err(_nchw(y), R.conv_ref(x.float().to(DEV), spec0)) < 1e-2
+
+
+@pytest.mark.parametrize("B,H,act,slices,grid", [(2, 5, "relu", True, 0), (4, 14, None, False, 1),
+                                                 (3, 30, "relu", False, 2)])
+def test_conv3x3_patchw_guarded(native, B, H, act, slices, grid):
+    """Variant 16: 14-row tiles; H = 5 / 30 end each image in a partial tile, grid 1 / 2 walks
+    several tiles per workgroup; a channel-slice input (pitch 192, gap channels poison)."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    g = torch.Generator().manual_seed(B * 100 + H)
+    spec0 = C.make_conv_spec(torch.randn(128, 128, 3, 3, generator=g) / (128 * 9) ** 0.5,
+                             torch.randn(128, generator=g) * 0.1, pad=1, act=act, device=DEV)
+    x = torch.randn(B, 128, H, 28, generator=g).to(BF16)
+    assert H % 14 != 0 or grid == 1
+
+    def case(ops):
+        spec = ops.spec(spec0)
+        xin = ops.inp_slice(_nhwc(x), 192, 32, "x") if slices else ops.inp(_nhwc(x), "x")
+        if slices:
+            ybig = ops.out((B, H, 28, 256), name="concat buffer")
+            out = ybig[..., 64:192]
+        else:
+            out = ops.out((B, H, 28, 128))
+        assert C.patchw_variant_ok(spec, xin, None, None, out)
+        torch.ops.aiko.conv3x3_patchw_out(xin, ops.inp(C.patchw_weight(spec), "weight image"), spec.bias, out,
+                                          spec.act, grid)
+        if slices:
+            torch.cuda.synchronize()
+            assert torch.isnan(ybig[..., :64].float()).all() and torch.isnan(ybig[..., 192:].float()).all()
+        return out
+
+    y = run_both(case)
+    assert _rel_err(_nchw(y), R.conv_ref(x.float().to(DEV), spec0)) < 1e-2
+
+
+@pytest.mark.parametrize("B,H,act,res,slices,grid", [(2, 1, None, "after", False, 1), (4, 3, "silu", None, True, 5),
+                                                     (3, 7, "relu", "before", True, 4)])
+def test_conv3x3_rows_guarded(native, B, H, act, res, slices, grid):
+    """Variant 17: B * H rows split over ``grid`` workgroups (12 over 5, 21 over 4: uneven
+    ranges crossing image boundaries); channel-slice input / residual / output."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    g = torch.Generator().manual_seed(B * 31 + H)
+    spec0 = C.make_conv_spec(torch.randn(32, 32, 3, 3, generator=g) / (32 * 9) ** 0.5,
+                             torch.randn(32, generator=g) * 0.1, pad=1, act=act, device=DEV)
+    x = torch.randn(B, 32, H, 80, generator=g).to(BF16)
+    r = torch.randn(B, 32, H, 80, generator=g).to(BF16) if res else None
+    if grid > 1:
+        assert (B * H) % grid != 0, "even row split"
+
+    def case(ops):
+        spec = ops.spec(spec0)
+        if slices:
+            xin = ops.inp_slice(_nhwc(x), 96, 32, "x")
+            rin = ops.inp_slice(_nhwc(r), 96, 64, "residual") if r is not None else None
+            ybig = ops.out((B, H, 80, 128), name="concat buffer")
+            out = ybig[..., 96:128]
+        else:
+            xin = ops.inp(_nhwc(x), "x")
+            rin = ops.inp(_nhwc(r), "residual") if r is not None else None
+            out = ops.out((B, H, 80, 32))
+        assert C.rows_variant_ok(spec, xin, rin, None, out)
+        act_code = spec.act | (C.ACT_RESIDUAL_AFTER if res == "after" else 0)
+        torch.ops.aiko.conv3x3_rows_out(xin, ops.inp(C.rows_weight(spec), "weight image"), spec.bias, rin, out,
+                                        act_code, grid)
+        if slices:
+            torch.cuda.synchronize()
+            assert torch.isnan(ybig[..., :96].float()).all()
+        return out
+
+    y = run_both(case)
+    ref = R.conv_ref(x.float().to(DEV), spec0, None if (r is None or res == "after") else r.float().to(DEV))
+    if res == "after":
+        ref = ref + r.float().to(DEV)
+    assert _rel_err(_nchw(y), ref) < 1e-2
+
+
+# ---- ResNet fused kernels ------------------------------------------------------------------------
+
+@pytest.mark.parametrize("B,H,W,grid", [(1, 8, 8, 0), (3, 8, 8, 2)])
+@pytest.mark.parametrize("k1,n1,n2", [(64, 256, 64), (64, 256, 128), (128, 512, 128)])
+def test_conv_chain_guarded(native, k1, n1, n2, B, H, W, grid):
+    """conv_chain / conv_chain2: 64-pixel tiles, M % 64 == 0 by contract (no partial tile); the
+    kernels prefetch the NEXT tile's rows, so the edge is the last tile of each workgroup's walk
+    (grid 2 over 3 tiles: an uneven walk)."""
+    from aiko_services_amd.ops import conv as C
+    g = torch.Generator().manual_seed(n2 + k1)
+    spec3 = C.make_conv_spec(torch.randn(n1, k1, 1, 1, generator=g) / k1 ** 0.5, 0.1 * torch.randn(n1, generator=g),
+                             act="relu", device=DEV)
+    spec1 = C.make_conv_spec(torch.randn(n2, n1, 1, 1, generator=g) / n1 ** 0.5, 0.1 * torch.randn(n2, generator=g),
+                             act="relu", device=DEV)
+    assert C.chain_ok(spec3, spec1)
+    x = torch.randn(B, H, W, k1, generator=g).to(BF16)
+    r = torch.randn(B, H, W, n1, generator=g).to(BF16)
+    M = B * H * W
+    assert M % 64 == 0
+    if grid:
+        assert (M // 64) % grid != 0, "even walk"
+
+    def case(ops):
+        y, z = ops.out((B, H, W, n1), name="y"), ops.out((B, H, W, n2), name="z")
+        C.conv_chain(ops.inp(x, "x"), ops.spec(spec3), ops.inp(r, "residual"), y, ops.spec(spec1), z, grid=grid)
+        return y, z
+
+    y, z = run_both(case)
+    xd, rd = x.to(DEV), r.to(DEV)
+    y2 = C.conv2d(xd, spec3, residual=rd)
+    z2 = C.conv2d(y2, spec1)
+    assert ((y.float() - y2.float()).abs() > 0.02 * (1 + y2.float().abs())).float().mean() < 1e-3
+    assert ((z.float() - z2.float()).abs().max() / z2.float().abs().max()) < 2e-2
+    yr = torch.relu(xd.float() @ spec3.ref_weight[:, :, 0, 0].T.to(DEV) + spec3.ref_bias.to(DEV) + rd.float())
+    assert ((y.float() - yr).norm() / yr.norm()).item() < 1e-2
+
+
+def _bneck_block(g, cin, dual):
+    from aiko_services_amd.models.resnet50 import _rand_bn, _rand_conv
+    from aiko_services_amd.ops import conv as C
+    c1 = C.make_conv_spec(*C.fold_bn(_rand_conv(g, 64, cin, 1), *_rand_bn(g, 64)), act="relu", device=DEV)
+    c2 = C.make_conv_spec(*C.fold_bn(_rand_conv(g, 64, 64, 3), *_rand_bn(g, 64)), pad=1, act="relu", device=DEV)
+    c3 = C.make_conv_spec(*C.fold_bn(_rand_conv(g, 256, 64, 1), *_rand_bn(g, 256, (0.1, 0.3))), act="relu",
+                          device=DEV)
+    down = None
+    if dual:
+        down = C.make_conv_spec(*C.fold_bn(_rand_conv(g, 256, cin, 1), *_rand_bn(g, 256)), device=DEV)
+    return c1, c2, c3, down
+
+
+def test_conv_chain_dual_guarded(native):
+    """The dual-source chain ([t2 | x] . W^T, K = 64 + 64 -> 256 -> 64) at M = 64: one tile."""
+    from aiko_services_amd.ops import conv as C
+    g = torch.Generator().manual_seed(3)
+    _, _, c3, down = _bneck_block(g, 64, True)
+    fused = C.fuse_shortcut(c3, down)
+    nxt = C.make_conv_spec(torch.randn(64, 256, 1, 1, generator=g) / 16, 0.1 * torch.randn(64, generator=g),
+                           act="relu", device=DEV)
+    assert C.chain_dual_ok(fused, nxt)
+    B, H, W = 1, 8, 8
+    t2 = torch.randn(B, H, W, 64, generator=g).to(BF16)
+    x = torch.randn(B, H, W, 64, generator=g).to(BF16)
+
+    def case(ops):
+        y, z = ops.out((B, H, W, 256), name="y"), ops.out((B, H, W, 64), name="z")
+        C.conv_chain(ops.inp(t2, "t2"), ops.spec(fused), None, y, ops.spec(nxt), z, x2=ops.inp(x, "x2"))
+        return y, z
+
+    y, z = run_both(case)
+    y2 = C.conv2d(t2.to(DEV), fused, x2=x.to(DEV))
+    z2 = C.conv2d(y2, nxt)
+    assert ((y.float() - y2.float()).norm() / y2.float().norm()).item() < 5e-3
+    assert ((z.float() - z2.float()).norm() / z2.float().norm()).item() < 1e-2
+
+
+@pytest.mark.parametrize("B,H,grid", [(1, 1, 1), (2, 3, 2), (3, 2, 0), (3, 3, 2)])
+@pytest.mark.parametrize("dual", [False, True])
+def test_bneck_fused_guarded(native, B, H, dual, grid):
+    """bneck_fused streams 56-pixel image rows through 64 pixel slots (a partial tile in every
+    row) over contiguous per-workgroup row ranges; (3, 3, 2): 9 rows over 2 workgroups."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    g = torch.Generator().manual_seed(B * 1000 + H * 10 + int(dual) + 7 * grid)
+    cin = 64 if dual else 256
+    c1, c2, c3, down = _bneck_block(g, cin, dual)
+    conv3 = C.fuse_shortcut(c3, down) if dual else c3
+    x = torch.relu(torch.randn(B, cin, H, 56, generator=g)).to(BF16)
+    assert 56 % 64 != 0
+    if (B, H, grid) == (3, 3, 2):
+        assert (B * H) % grid != 0, "even row split"
+
+    def case(ops):
+        out = ops.out((B, H, 56, 256))
+        C.bneck_fused(ops.inp(_nhwc(x), "x"), ops.spec(c1, "conv1"), ops.spec(c2, "conv2"), ops.spec(conv3, "conv3"),
+                      out=out, grid=grid)
+        return out
+
+    y = run_both(case)
+    xf = x.float().to(DEV)
+    t = R.conv_ref(xf, c1)
+    t = R.conv_ref(t.to(BF16).float(), c2)
+    idn = R.conv_ref(xf, down) if down is not None else xf
+    ref = R.conv_ref(t.to(BF16).float(), c3, residual_nchw=idn)
+    err = _rel_err(_nchw(y), ref)
+    assert err < 1e-2, err
+
+
+@pytest.mark.parametrize("B,H,W,N,grid", [(1, 14, 14, 1024, 0), (3, 14, 14, 1024, 2), (5, 7, 9, 512, 1)])
+def test_conv3x3_exp_guarded(native, B, H, W, N, grid):
+    """conv_exp.hip: 256-row tiles, M = 196 / 588 / 315: the last tile is partial."""
+    from aiko_services_amd.models.resnet50 import _rand_bn, _rand_conv
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    g = torch.Generator().manual_seed(B * 1000 + H * 10 + W + N + 7 * grid)
+    c2 = C.make_conv_spec(*C.fold_bn(_rand_conv(g, 256, 256, 3), *_rand_bn(g, 256)), pad=1, act="relu", device=DEV)
+    c3 = C.make_conv_spec(*C.fold_bn(_rand_conv(g, N, 256, 1), *_rand_bn(g, N, (0.1, 0.3))), act="relu", device=DEV)
+    t1 = torch.relu(torch.randn(B, 256, H, W, generator=g)).to(BF16)
+    x = torch.relu(torch.randn(B, N, H, W, generator=g)).to(BF16)
+    M = B * H * W
+    assert M % 256 != 0
+
+    def case(ops):
+        out = ops.out((B, H, W, N))
+        s2, s3 = ops.spec(c2, "conv2"), ops.spec(c3, "conv3")
+        t1d, xd = ops.inp(_nhwc(t1), "t1"), ops.inp(_nhwc(x), "residual")
+        assert C.conv_exp_ok(s2, s3, t1d, xd)
+        C.conv3x3_exp(t1d, s2, s3, xd, out=out, grid=grid)
+        return out
+
+    y = run_both(case)
+    t = R.conv_ref(t1.float().to(DEV), c2)
+    ref = _nhwc(R.conv_ref(t.to(BF16).float(), c3, residual_nchw=x.float().to(DEV))).reshape(M, N)
+    a = y.reshape(M, N).float()
+    for r0 in range(0, M, 256):                                 # the per-tile bound of test_gpu_conv_exp
+        e = _rel_err(a[r0:r0 + 256], ref[r0:r0 + 256])
+        assert e < 1e-2, (r0, e)
+
+
+# ---- stems ---------------------------------------------------------------------------------------
+
+@pytest.fixture(scope="module")
+def stem_case():
+    from aiko_services_amd.ops import conv as C
+    g = torch.Generator().manual_seed(11)
+    hw = (96, 132)
+    frames = torch.randint(0, 256, (2, hw[0], hw[1], 3), generator=g, dtype=torch.uint8)
+    w = torch.randn(64, 3, 7, 7, generator=g) / (3 * 49) ** 0.5
+    b = torch.randn(64, generator=g) * 0.1
+    spec = C.make_stem_spec(w, b, act="relu", device=DEV)
+    return hw, frames, spec
+
+
+def _stem_ref(frames, spec, hw, pool):
+    from aiko_services_amd.ops import reference as R
+    xr = R.preprocess_ref(frames.to(DEV), hw)
+    y = R.conv_ref(xr.to(BF16).float(), spec)
+    return F.max_pool2d(y, 3, 2, 1) if pool else y
+
+
+def test_preprocess_and_stem_conv_guarded(native, stem_case):
+    """preprocess_frames (row kernel: aligned base) -> the stem through conv2d(image_hw=...),
+    M = 2 * 48 * 66 = 6336 on 128-row tiles (a 64-row tail)."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    from aiko_services_amd.ops import vision as V
+    hw, frames, spec0 = stem_case
+    B = frames.shape[0]
+    Hp, Wp = C.stem_geometry(*hw)
+    Ho, Wo = spec0.out_hw(*hw)
+    assert (B * Ho * Wo) % 128 != 0
+
+    def case(ops):
+        pre = V.preprocess_frames(ops.inp(frames, "frames"), hw, out=ops.out((B, Hp, Wp, 4), name="stem buffer"))
+        out = ops.out((B, Ho, Wo, 64))
+        C.conv2d(pre, ops.spec(spec0), image_hw=hw, out=out, tile=(128, 64))
+        return pre, out
+
+    pre, y = run_both(case)
+    xr = R.preprocess_ref(frames.to(DEV), hw)
+    assert _rel_err(_nchw(pre[:, 3:3 + hw[0], 3:3 + hw[1], :3]), xr) < 5e-3
+    assert pre[:, :3].abs().max().item() == 0 and pre[..., 3].abs().max().item() == 0
+    assert pre[:, :, :3].abs().max().item() == 0 and pre[:, :, 3 + hw[1]:].abs().max().item() == 0
+    assert _rel_err(_nchw(y), _stem_ref(frames, spec0, hw, False)) < 1e-2
+
+
+@pytest.mark.parametrize("variant", [0, 1])
+def test_stem_pool_guarded(native, stem_case, variant):
+    """Fused stem + max-pool: pooled tiles of 8 x 7 / 8 x 14 over a 24 x 33 pooled image."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import vision as V
+    hw, frames, spec0 = stem_case
+    B = frames.shape[0]
+    Ho, Wo = spec0.out_hw(*hw)
+    Hm, Wm = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
+    assert Wm % (7, 14)[variant] != 0
+    pre0 = V.preprocess_frames(frames.to(DEV), hw)
+
+    def case(ops):
+        out = ops.out((B, Hm, Wm, 64))
+        C.stem_pool(ops.inp(pre0, "stem buffer"), ops.spec(spec0), hw, out=out, variant=variant)
+        return out
+
+    y = run_both(case)
+    assert _rel_err(_nchw(y), _stem_ref(frames, spec0, hw, True)) < 1e-2
+    unfused = V.maxpool2d(C.conv2d(pre0, spec0, image_hw=hw), 3, 2, 1)
+    assert torch.equal(y, unfused)
+
+
+@pytest.mark.parametrize("variant", [0, 1, 2, 3, 4])
+def test_stem_pool_u8_guarded(native, stem_case, variant):
+    """uint8 frames straight into the fused stem: the image edges are tap masks on the FRAME
+    (no zero-bordered buffer), so the guards sit directly against rows 0 and H-1."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import vision as V
+    hw, frames, spec0 = stem_case
+    B = frames.shape[0]
+    Ho, Wo = spec0.out_hw(*hw)
+    Hm, Wm = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
+    assert Wm % 7 != 0 and hw[1] % 4 == 0
+
+    def case(ops):
+        out = ops.out((B, Hm, Wm, 64))
+        C.stem_pool_u8(ops.inp(frames, "frames"), ops.spec(spec0), V.IMAGENET_MEAN, V.IMAGENET_STD, out=out,
+                       variant=variant)
+        return out
+
+    y = run_both(case)
+    assert _rel_err(_nchw(y), _stem_ref(frames, spec0, hw, True)) < 1e-2
+
+
+@pytest.fixture(scope="module")
+def yolo(native):
+    from aiko_services_amd.models.yolov8 import YOLOv8
+    return YOLOv8("n", device=DEV)
+
+
+@pytest.mark.parametrize("hw,S", [((360, 500), 640), ((120, 200), 200), ((90, 125), 200)])
+def test_stem_direct_guarded(native, yolo, hw, S):
+    """stem_direct_out: (360, 500) -> 640 is the resizing kernel at the model's geometry; the
+    200 x 200 canvases give a 100 x 100 output (partial 16 x 32 tiles) without (120, 200: the
+    fast kernel) and with (90, 125) a resize, letterbox bars above and below."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    from aiko_services_amd.ops import vision as V
+    m = yolo
+    g = torch.Generator().manual_seed(hw[0])
+    B = 2
+    frames = torch.randint(0, 256, (B,) + hw + (3,), generator=g, dtype=torch.uint8)
+    Ho, Wo, top, left, _ = V.letterbox_geometry(hw[0], hw[1], S)
+    h0, w0 = C.stem_out_hw(S, S, 3, 2, 1)
+    if S != 640:
+        assert h0 % 16 != 0 and w0 % 32 != 0
+    if m._stem_w is None:
+        m.stem_from_frames(frames.to(DEV))
+    stem_w = m._stem_w.clone()
+
+    def case(ops):
+        out = ops.out((B, h0, w0, m.ch[0]))
+        torch.ops.aiko.stem_direct_out(ops.inp(frames, "frames"), ops.inp(stem_w, "weight"), ops.inp(m.l0.bias, "bias"),
+                                       out, [Ho, Wo, S, S, top, left, 3, 2, 1, 2], 114.0, list(V.YOLO_MEAN),
+                                       list(V.YOLO_STD), False)
+        return out
+
+    y = run_both(case)
+    Hp, Wp = C.stem_geometry(S, S, 3, 2, 1)
+    pre = V.preprocess_frames(frames.to(DEV), (Ho, Wo), V.YOLO_MEAN, V.YOLO_STD, stem=(3, 2, 1),
+                              out=torch.empty(B, Hp, Wp, 4, dtype=BF16, device=DEV), canvas=(S, S, top, left, 114.0))
+    unfused = C.conv2d(pre, m.l0, image_hw=(S, S))
+    assert _rel_err(y.float(), unfused.float()) < 5e-3
+    ref = R.conv_ref(_nchw(pre[:, 1:S + 1, 1:S + 1, :3]).float(), m.l0)
+    assert _rel_err(_nchw(y), ref) < 1e-2
+
+
+# ---- YOLO fused kernels --------------------------------------------------------------------------
+
+def _c2f_bound(a, b):
+    a, b = a.float(), b.float()
+    cos = F.cosine_similarity(a.flatten(), b.flatten(), dim=0).item()
+    assert cos > 0.9995, cos
+    assert (a - b).abs().max().item() < 0.05 * b.abs().max().item()
+
+
+@pytest.mark.parametrize("layer,H,W,cin,cout,rb", [
+    ("l2", 160, 160, 32, 32, 10), ("l2", 160, 160, 32, 32, 20), ("l2", 160, 160, 32, 32, 160),
+    ("l15", 80, 80, 192, 64, 10), ("l15", 80, 80, 192, 64, 20), ("l15", 80, 80, 192, 64, 80)])
+def test_c2f_fused_guarded(native, yolo, monkeypatch, layer, H, W, cin, cout, rb):
+    """c2f_fused.hip (l2: weights in registers; l15: the LDS-weights variant), one workgroup per
+    band of rb rows: halo rows recomputed at band edges, zero rows at the image edges; rb == H is
+    the single band with zero rows on both sides and no halo.  The launcher refuses
+    H % rb != 0, so no band is partial."""
+    from aiko_services_amd.models.yolov8 import YOLOv8
+    m, blk = yolo, getattr(yolo, layer)
+    g = torch.Generator().manual_seed(rb)
+    x = (torch.randn(1, H, W, cin, generator=g) * 2).to(BF16)
+    a, b = blk.m[0]
+    assert H % rb == 0
+
+    def case(ops):
+        out = ops.out((1, H, W, cout))
+        xd = ops.inp(x, "x")
+        assert m._c2f_fused_ok(blk, xd, out)
+        sp = [ops.spec(s, n) for s, n in ((blk.cv1, "cv1"), (a, "m.a"), (b, "m.b"), (blk.cv2, "cv2"))]
+        torch.ops.aiko.c2f_fused_out(xd, sp[0].weight, sp[0].bias, sp[1].weight, sp[1].bias, sp[2].weight, sp[2].bias,
+                                     sp[3].weight, sp[3].bias, out, blk.cv1.Cc, blk.shortcut, rb, None)
+        return out
+
+    y = run_both(case)
+    monkeypatch.setenv("AIKO_C2F_FUSED", "0")
+    out_u = torch.empty_like(y)
+    m._run_c2f(layer + "g", blk, x.to(DEV), out_u)
+    torch.cuda.synchronize()
+    _c2f_bound(y, out_u)
+
+
+def test_c2f_fused_upsample_guarded(native, yolo):
+    """l15's fused C2f reading channels [0, 128) of its input as the nearest 2x upsample of
+    ``xu`` (a channel slice of a 192-channel buffer): those channels of ``x`` are never
+    materialised — poison in the guarded run — and must not be read.  Bit-identical to the same
+    kernel on the materialised input."""
+    m, blk = yolo, yolo.l15
+    g = torch.Generator().manual_seed(15)
+    H = W = 80
+    rb = 10
+    tail = (torch.randn(1, H, W, 64, generator=g) * 2).to(BF16)
+    xu0 = (torch.randn(1, H // 2, W // 2, 128, generator=g) * 2).to(BF16)
+    a, b = blk.m[0]
+
+    def launch(xd, xu, out, sp):
+        torch.ops.aiko.c2f_fused_out(xd, sp[0].weight, sp[0].bias, sp[1].weight, sp[1].bias, sp[2].weight, sp[2].bias,
+                                     sp[3].weight, sp[3].bias, out, blk.cv1.Cc, blk.shortcut, rb, xu)
+
+    def case(ops):
+        wide = torch.full((1, H, W, 192), NAN if ops.on else 0.0, dtype=BF16)
+        wide[..., 128:] = tail
+        out = ops.out((1, H, W, 64))
+        xd = ops.inp(wide, "x")
+        assert m._c2f_fused_ok(blk, xd, out)
+        launch(xd, ops.inp_slice(xu0, 192, 64, "upsample source"), out,
+               [ops.spec(s, n) for s, n in ((blk.cv1, "cv1"), (a, "m.a"), (b, "m.b"), (blk.cv2, "cv2"))])
+        return out
+
+    y = run_both(case)
+    up = xu0.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
+    ref = torch.empty_like(y)
+    launch(torch.cat([up, tail], -1).to(DEV), None, ref, [blk.cv1, a, b, blk.cv2])
+    torch.cuda.synchronize()
+    assert torch.equal(y, ref)
+
+
+@pytest.mark.parametrize("rb", [10, 20, 80])
+def test_c2f_bneck_guarded(native, yolo, monkeypatch, rb):
+    """c2f_bneck_kernel on l4's first bottleneck: reads channels [32, 64) and writes channels
+    [64, 96) of the 128-channel concat buffer; every other channel of it is poison.  Bands of
+    10 / 20 rows (the existing test's) and the single band rb == H."""
+    from aiko_services_amd.ops import conv as C
+    m, blk = yolo, yolo.l4
+    g = torch.Generator().manual_seed(10)
+    H = W = 80
+    c = blk.c
+    assert c == 32 and blk.shortcut and H % rb == 0
+    x = (torch.randn(1, H, W, c, generator=g) * 2).to(BF16)
+    a, b = blk.m[0]
+
+    def case(ops):
+        wide = torch.full((1, H, W, 4 * c), NAN, dtype=BF16)
+        wide[..., c:2 * c] = x
+        cat = ops.inp(wide, "concat buffer")
+        sa, sb = ops.spec(a, "m.a"), ops.spec(b, "m.b")
+        torch.ops.aiko.c2f_bneck_out(cat[..., c:2 * c], sa.weight, sa.bias, sb.weight, sb.bias, cat[..., 2 * c:3 * c],
+                                     blk.shortcut, rb)
+        torch.cuda.synchronize()
+        assert torch.isnan(cat[..., :c].float()).all() and torch.isnan(cat[..., 3 * c:].float()).all()
+        assert torch.equal(cat[..., c:2 * c], x.to(DEV))
+        return cat[..., 2 * c:3 * c]
+
+    y = run_both(case)
+    xd = x.to(DEV)
+    t = C.conv2d(xd, a)
+    ref = C.conv2d(t, b, residual=xd, residual_after_act=True)
+    _c2f_bound(y, ref)
+
+
+@pytest.mark.parametrize("branch,hw", [("box", 20), ("cls", 20), ("box", 40), ("cls", 40), ("box", 80), ("cls", 80),
+                                       ("l3", None)])
+def test_conv_tail_guarded(native, yolo, branch, hw):
+    """conv_glds TAIL (3x3 + SiLU with the 1x1 in its epilogue, 128-row tiles), B = 1.  box / cls:
+    the three head levels (20 x 20 and 40 x 40 end in a partial tile, 80 x 80 = 50 whole tiles),
+    input and output channel slices of [.., 64 + 80] buffers whose other slice is poison.  l3:
+    the 3x3 / stride 2 conv 32 -> 64 with l4's cv1 (1x1 + SiLU) in its epilogue on an odd 21 x 19
+    image, from a slice of a 48-channel buffer into the first half of l4's concat."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    lvl = yolo.heads[0]
+    s1, s2, cin, c0, pitch, n, o0, opitch, H, W = {
+        "box": (lvl.box[1], lvl.box[2], 64, 0, 144, 64, 0, 144, hw, hw),
+        "cls": (lvl.cls[1], lvl.cls[2], 80, 64, 144, 80, 64, 144, hw, hw),
+        "l3": (yolo.l3, yolo.l4.cv1, 32, 16, 48, 64, 0, 128, 21, 19)}[branch]
+    g = torch.Generator().manual_seed(20)
+    x = (torch.randn(1, H, W, cin, generator=g) * 2).to(BF16)
+    Ho, Wo = s1.out_hw(H, W)
+    M = Ho * Wo
+    if hw != 80:
+        assert n in (64, 80) and M % 128 != 0, "no partial last tile"
+
+    def case(ops):
+        xs = ops.inp_slice(x, pitch, c0, "input buffer")
+        big = ops.out((1, Ho, Wo, opitch), name="output buffer")
+        a, b = ops.spec(s1, "3x3"), ops.spec(s2, "1x1")
+        assert C.conv_tail_ok(xs, a, b)
+        C.conv2d_tail(xs, a, b, big[..., o0:o0 + n])
+        torch.cuda.synchronize()
+        other = torch.cat([big[..., :o0], big[..., o0 + n:]], -1)
+        assert torch.isnan(other.float()).all(), "wrote outside the output's channel slice"
+        return big[..., o0:o0 + n]
+
+    y = run_both(case)
+    xr = _nchw(x.to(DEV).float())
+    yr = _nhwc(R.conv_ref(R.conv_ref(xr, s1), s2))
+    assert ((y.float() - yr).norm() / yr.norm()).item() < 1e-2
+    t = C.conv2d(x.to(DEV), s1)
+    ref = C.conv2d(t, s2).float()
+    assert F.cosine_similarity(y.float().flatten(), ref.flatten(), dim=0).item() > 0.9999
+    assert (y.float() - ref).abs().max().item() < 0.02 * ref.abs().max().item()
+
+
+def test_conv_tail_decode_guarded(native):
+    """The tail launches that decode in their epilogue (box: DFL -> xyxy; class: sigmoid(max) /
+    argmax) writing rows [astart, astart + H * W) of [B, A] outputs: the anchors before and after
+    the level are poison and must stay so.  Against the stored head output + yolo_decode."""
+    from aiko_services_amd.models import yolov8 as Y
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import detect as DT
+    m = Y.YOLOv8("n", device=DEV, cls_bias=0.0)
+    assert m._decode_fused_ok()
+    lvl = m.heads[1]
+    g = torch.Generator().manual_seed(13)
+    B, H, W = 1, 20, 20
+    M, astart, A = H * W, 24, H * W + 64
+    assert M % 64 != 0 and M % 128 != 0 and M % 256 != 0
+    h1 = (torch.randn(B, H, W, 144, generator=g) * 2).to(BF16)
+
+    def case(ops):
+        hd = ops.inp(h1, "head buffer")
+        zp = C.zero_page(hd.device)
+        boxes = ops.out((B, A, 4), torch.float32, "boxes")
+        scores = ops.out((B, A), torch.float32, "scores")
+        cls = ops.out((B, A), torch.int32, "cls")
+        if not ops.on:
+            cls.fill_(-1515870811)                           # 0xA5A5A5A5: the guarded run's poison
+        for xs, (s1, s2), mode, nc in ((hd[..., :64], (lvl.box[1], lvl.box[2]), 1, 64),
+                                       (hd[..., 64:], (lvl.cls[1], lvl.cls[2]), 2, 80)):
+            a, b = ops.spec(s1), ops.spec(s2)
+            torch.ops.aiko.conv_glds_tail_decode_out(xs, a.weight, a.bias, b.weight, b.bias, boxes, scores, cls,
+                                                     s1.R, s1.pad, s1.act, mode, nc, 16, astart, zp)
+        torch.cuda.synchronize()
+        for t in (boxes, scores):
+            assert torch.isnan(t[:, :astart]).all() and torch.isnan(t[:, astart + M:]).all()
+        assert (cls[:, :astart] == -1515870811).all() and (cls[:, astart + M:] == -1515870811).all()
+        return boxes[:, astart:astart + M], scores[:, astart:astart + M], cls[:, astart:astart + M]
+
+    bf, sf, cf = run_both(case)
+    hd = h1.to(DEV)
+    feat = torch.empty(B, H, W, 144, dtype=BF16, device=DEV)
+    C.conv2d_tail(hd[..., :64], lvl.box[1], lvl.box[2], feat[..., :64])
+    C.conv2d_tail(hd[..., 64:], lvl.cls[1], lvl.cls[2], feat[..., 64:])
+    bd, sd, cd = DT.yolo_decode([feat], (16,), 80)
+    torch.cuda.synchronize()
+    assert torch.equal(cf, cd) and torch.equal(sf, sd)
+    assert (bf - bd).abs().max().item() < 1e-3 * bd.abs().max().item()
+
+
+# ---- pointwise ops -------------------------------------------------------------------------------
+
+# The launchers in vision_ops.hip / detect_ops.hip: one thread per output element (a pixel, or 8
+# channels of a pixel) in blocks of 256 threads, or one wave per row in blocks of 4 waves.  Each
+# case computes that split and asserts the last block is partial.
+BLOCK = 256
+WAVES = 4
+
+
+def test_preprocess_rows_guarded(native):
+    """No-resize frames at an aligned base: preprocess_rows_kernel (dword loads, a wave per row;
+    W * 3 = 300 bytes per row), BGR; the zero border is written over the output's poison."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    from aiko_services_amd.ops import vision as V
+    g = torch.Generator().manual_seed(136)
+    B, H, W = 3, 36, 100
+    frames = torch.randint(0, 256, (B, H, W, 3), generator=g, dtype=torch.uint8)
+    Hp, Wp = C.stem_geometry(H, W)
+    assert Hp % WAVES != 0, "a wave per output row, 4 rows per block: no partial block"
+    assert (W * 3 // 4) % 64 != 0 and Wp % 64 != 0, "no partial 64-lane pass over a row"
+
+    def case(ops):
+        fr = ops.inp(frames, "frames")
+        assert fr.data_ptr() % 4 == 0
+        return V.preprocess_frames(fr, (H, W), bgr=True, out=ops.out((B, Hp, Wp, 4)))
+
+    pre = run_both(case)
+    ref = R.preprocess_ref(frames.to(DEV), (H, W), bgr=True)
+    assert _rel_err(_nchw(pre[:, 3:3 + H, 3:3 + W, :3]), ref) < 5e-3
+    assert pre[:, :3].abs().max().item() == 0 and pre[..., 3].abs().max().item() == 0
+    assert pre[:, :, :3].abs().max().item() == 0 and pre[:, :, 3 + W:].abs().max().item() == 0
+    assert pre[:, 3 + H:].abs().max().item() == 0
+
+
+def test_preprocess_resize_guarded(native):
+    """The resizing kernel: a thread per stem-buffer pixel, blocks of 256 per image."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    from aiko_services_amd.ops import vision as V
+    g = torch.Generator().manual_seed(5)
+    frames = torch.randint(0, 256, (2, 480, 640, 3), generator=g, dtype=torch.uint8)
+    Hp, Wp = C.stem_geometry(224, 224)
+    assert (Hp * Wp) % BLOCK != 0 and Hp * Wp <= 1024 * BLOCK, "no partial last block per image"
+
+    def case(ops):
+        return V.preprocess_frames(ops.inp(frames, "frames"), (224, 224), out=ops.out((2, Hp, Wp, 4)))
+
+    pre = run_both(case)
+    ref = R.preprocess_ref(frames.to(DEV), (224, 224))
+    assert _rel_err(_nchw(pre[:, 3:227, 3:227, :3]), ref) < 1e-2
+
+
+def test_preprocess_letterbox_guarded(native):
+    """The YOLO form: /255 into a 200 x 200 canvas of colour 114 (bars above and below the
+    120-row frame) inside the 1-pixel zero border of a 3x3 / 2 stem buffer."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import vision as V
+    g = torch.Generator().manual_seed(7)
+    B, H, W, S = 2, 120, 200, 200
+    frames = torch.randint(0, 256, (B, H, W, 3), generator=g, dtype=torch.uint8)
+    Ho, Wo, top, left, _ = V.letterbox_geometry(H, W, S)
+    assert (Ho, Wo, top, left) == (120, 200, 40, 0)
+    Hp, Wp = C.stem_geometry(S, S, 3, 2, 1)
+    assert (Hp * Wp) % BLOCK != 0 and Hp * Wp <= 1024 * BLOCK, "no partial last block per image"
+
+    def case(ops):
+        return V.preprocess_frames(ops.inp(frames, "frames"), (Ho, Wo), V.YOLO_MEAN, V.YOLO_STD,
+                                   out=ops.out((B, Hp, Wp, 4)), stem=(3, 2, 1), canvas=(S, S, top, left, 114.0))
+
+    pre = run_both(case)
+    canvas = torch.full((B, 3, S, S), 114.0 / 255, device=DEV)
+    canvas[:, :, top:top + Ho, left:left + Wo] = _nchw(frames.to(DEV)).float() / 255
+    assert _rel_err(_nchw(pre[:, 1:S + 1, 1:S + 1, :3]), canvas) < 5e-3
+    assert pre[:, 0].abs().max().item() == 0 and pre[:, :, 0].abs().max().item() == 0
+    assert pre[:, S + 1:].abs().max().item() == 0 and pre[:, :, S + 1:].abs().max().item() == 0
+    assert pre[..., 3].abs().max().item() == 0
+
+
+def test_resize_u8_guarded(native):
+    """A thread per output pixel: 2 * 63 * 80 = 10080 pixels = 39 blocks and 96 threads."""
+    from aiko_services_amd.ops import vision as V
+    g = torch.Generator().manual_seed(6)
+    B, Ho, Wo = 2, 63, 80
+    frames = torch.randint(0, 256, (B, 37, 53, 3), generator=g, dtype=torch.uint8)
+    assert (B * Ho * Wo) % BLOCK != 0, "no partial last block"
+
+    def case(ops):
+        return V.resize_u8(ops.inp(frames, "frames"), (Ho, Wo), out=ops.out((B, Ho, Wo, 3), torch.uint8))
+
+    y = run_both(case)
+    ref = F.interpolate(_nchw(frames.to(DEV)).float(), size=(Ho, Wo), mode="bilinear",
+                        align_corners=False).round().clamp(0, 255).permute(0, 2, 3, 1)
+    assert (y.float() - ref).abs().max().item() <= 1
+
+
+def test_maxpool_guarded(native):
+    """3x3 / 2 / pad 1 on odd sizes (taps outside the first and the last image), and the 5x5 / 1
+    pool between channel slices of one concat buffer (SPPF form).  A thread per 8 channels of an
+    output pixel.  Run with NaN and with +3e38 in the guards: the kernel's max drops a NaN tap."""
+    from aiko_services_amd.ops import vision as V
+    g = torch.Generator().manual_seed(11)
+    x = torch.randn(2, 13, 15, 64, generator=g).to(BF16)
+    cat0 = torch.randn(3, 20, 20, 128, generator=g).to(BF16)
+    assert (2 * 7 * 8 * (64 // 8)) % BLOCK != 0 and (3 * 20 * 20 * (32 // 8)) % BLOCK != 0, "no partial last block"
+
+    def case(ops):
+        y = V.maxpool2d(ops.inp(x, "x"), 3, 2, 1, out=ops.out((2, 7, 8, 64)))
+        cat = ops.inp(cat0, "concat buffer")
+        V.maxpool2d(cat[..., :32], 5, 1, 2, out=cat[..., 32:64])
+        return y, cat
+
+    run_both(case, poison=3e38)
+    y, cat = run_both(case)
+    assert torch.equal(_nchw(y).float(), F.max_pool2d(_nchw(x.to(DEV)).float(), 3, 2, 1))
+    assert torch.equal(_nchw(cat[..., 32:64]).float(), F.max_pool2d(_nchw(cat0[..., :32].to(DEV)).float(), 5, 1, 2))
+    keep = torch.cat([cat[..., :32], cat[..., 64:]], -1)
+    assert torch.equal(keep, torch.cat([cat0[..., :32], cat0[..., 64:]], -1).to(DEV))
+
+
+def test_avgpool_upsample_guarded(native):
+    from aiko_services_amd.ops import detect as DT
+    from aiko_services_amd.ops import vision as V
+    g = torch.Generator().manual_seed(12)
+    Ca = 2040                                    # 3 * 255 threads: the last block is partial
+    x = torch.randn(3, 7, 7, Ca, generator=g).to(BF16)
+    u = torch.randn(2, 5, 7, 32, generator=g).to(BF16)
+    assert (3 * (Ca // 8)) % BLOCK != 0, "avgpool (a thread per 8 channels of an image): no partial last block"
+    assert (7 * (32 // 8)) % BLOCK != 0, "upsample2x (a thread per 8 channels of an input row pixel): no partial block"
+
+    def case(ops):
+        a = V.avgpool(ops.inp(x, "x"), out=ops.out((3, Ca)))
+        big = ops.out((2, 10, 14, 80), name="concat buffer")
+        DT.upsample2x(ops.inp_slice(u, 48, 16, "x slice"), out=big[..., 48:80])
+        torch.cuda.synchronize()
+        assert torch.isnan(big[..., :48].float()).all()
+        return a, big[..., 48:80]
+
+    a, up = run_both(case)
+    assert _rel_err(a, x.to(DEV).float().mean(dim=(1, 2))) < 5e-3
+    ref = F.interpolate(_nchw(u.to(DEV)).float(), scale_factor=2, mode="nearest").permute(0, 2, 3, 1)
+    assert torch.equal(up.float(), ref)
+
+
+@pytest.mark.parametrize("B,H,W,c", [(2, 7, 33, 16), (3, 20, 20, 128)])
+def test_sppf_pool_guarded(native, B, H, W, c):
+    """A block per (8 channels, image), its 256 threads striding over the H * W pixels.  Run with
+    NaN and with +3e38 in the guards: the kernel's max drops a NaN tap."""
+    from aiko_services_amd.ops import vision as V
+    g = torch.Generator().manual_seed(H * W + c)
+    cat0 = (torch.randn(B, H, W, 4 * c, generator=g) * 4).round().to(BF16)
+    assert (H * W) % BLOCK != 0, "no partial last pass over the image"
+
+    def case(ops):
+        return V.sppf_pool(ops.inp(cat0, "concat buffer"), c, 5)
+
+    run_both(case, poison=3e38)
+    cat = run_both(case)
+    ref = cat0.to(DEV).clone()
+    for i in range(3):
+        V.maxpool2d(ref[..., i * c:(i + 1) * c], 5, 1, 2, out=ref[..., (i + 1) * c:(i + 2) * c])
+    torch.cuda.synchronize()
+    assert torch.equal(cat, ref)
+
+
+def test_batchnorm_guarded(native):
+    from aiko_services_amd.ops import vision as V
+    g = torch.Generator().manual_seed(9)
+    x = torch.randn(2, 9, 11, 32, generator=g).to(BF16)
+    gamma, beta = torch.rand(32, generator=g) + 0.5, torch.randn(32, generator=g)
+    mean, var = torch.randn(32, generator=g), torch.rand(32, generator=g) + 0.5
+    scale, shift = V.bn_scale_shift(gamma, beta, mean, var)
+    assert (2 * 9 * 11 * (32 // 8)) % BLOCK != 0, "a thread per 8 channels of a pixel: no partial last block"
+
+    def case(ops):
+        big = ops.out((2, 9, 11, 64), name="concat buffer")
+        V.batchnorm(ops.inp_slice(x, 64, 32, "x slice"), ops.inp(scale, "scale"), ops.inp(shift, "shift"), act=1,
+                    out=big[..., :32])
+        torch.cuda.synchronize()
+        assert torch.isnan(big[..., 32:].float()).all()
+        return big[..., :32]
+
+    y = run_both(case)
+    ref = F.batch_norm(_nchw(x.to(DEV)).float(), mean.to(DEV), var.to(DEV), gamma.to(DEV), beta.to(DEV), False, 0.0,
+                       1e-5).relu()
+    assert _rel_err(_nchw(y), ref) < 1e-2
+
+
+def test_softmax_topk_guarded(native):
+    from aiko_services_amd.ops import vision as V
+    N, k = 1000, 5
+    g = torch.Generator().manual_seed(N)
+    lg = torch.randint(-4, 5, (19, N), generator=g).float()
+    lg[:, ::3] *= -0.0
+    lg = lg.to(BF16)
+    assert lg.shape[0] % WAVES != 0, "a wave per row, 4 rows per block: no partial last block"
+    assert 64 * 4 < N <= 64 * 16 and N % 64 != 0, "no partial 64-lane pass over a row (the 16-per-lane kernel)"
+
+    def case(ops):
+        return V.softmax_topk(ops.inp(lg, "logits"), k, prob=ops.out((19, k), torch.float32, "prob"),
+                              index=ops.out((19, k), torch.int32, "index"))
+
+    p, i = run_both(case)
+    order = torch.stack([torch.tensor(sorted(range(N), key=lambda c: (-float(r[c]), c))) for r in lg.float()])[:, :k]
+    assert torch.equal(i.cpu().long(), order)
+    assert torch.allclose(p.cpu(), torch.softmax(lg.float(), -1).gather(1, order), rtol=1e-4, atol=1e-6)
+
+
+@pytest.mark.parametrize("B,N,K", [(37, 1000, 2048), (1, 64, 1024)])
+def test_linear_guarded(native, B, N, K):
+    """The igemm linear and the split-K linear with a guarded ``work`` buffer of exactly
+    S * B * N elements (32 x 32 one-wave tiles: M = 37 / 1 and N = 1000 end in partial tiles)."""
+    from aiko_services_amd.ops import conv as C
+    from aiko_services_amd.ops import reference as R
+    g = torch.Generator().manual_seed(B + N)
+    spec0 = C.make_linear_spec(torch.randn(N, K, generator=g) * 0.02, torch.randn(N, generator=g), device=DEV)
+    x = torch.randn(B, K, generator=g).to(BF16)
+    assert B % 32 != 0 and (N % 32 != 0 or B == 1), "split-K: no partial 32 x 32 tile"
+    pick = C.pick_tile(B, N)
+    assert B % pick[0] != 0 and (N % pick[1] != 0 or B == 1), "igemm: no partial tile"
+
+    def case(ops):
+        spec, xd = ops.spec(spec0), ops.inp(x, "x")
+        assert C.linear_splitk_ok(xd, spec)
+        work = ops.out((C.LINEAR_SPLITK * B * N,), torch.float32, "work")
+        y1 = C.linear(xd, spec, out=ops.out((B, N), name="split-K y"), work=work)
+        y0 = C.linear(xd, spec, out=ops.out((B, N), name="igemm y"))
+        return y1, y0
+
+    y1, y0 = run_both(case)
+    ref = R.linear_ref(x.to(DEV).float(), spec0)
+    assert _rel_err(y1, ref) < 1e-2
+    assert _rel_err(y0, ref) < 1e-2
+    assert _rel_err(y1.float(), y0.float()) < 1e-2
+
+
+# ---- whole models on a guarded workspace ---------------------------------------------------------
+#
+# The per-kernel cases above force one tile each.  Here every activation buffer of a model's
+# workspace is a guarded view (``_buf`` swapped), so each kernel runs with the tile the model
+# picks, on the views the model makes: batch slices ``buf[c0:c0 + ch]`` of full-batch buffers,
+# channel slices of concat buffers, buffers only partly written by design.
+
+def _guard_workspace(m, monkeypatch):
+    checks, ws = [], {}
+
+    def _buf(key, shape, dtype=BF16):
+        k = (getattr(m, "ws_tag", "") + key, tuple(shape), dtype)
+        if k not in ws:
+            ws[k], check = guarded(shape, dtype, DEV, name=key)
+            checks.append(check)
+        return ws[k]
+
+    monkeypatch.setattr(m, "_buf", _buf)
+    return checks
+
+
+@pytest.fixture(scope="module")
+def resnet(native):
+    from aiko_services_amd.models.resnet50 import ResNet50
+    m = ResNet50(seed=0, device=DEV)
+    g = torch.Generator().manual_seed(0)
+    frames = torch.randint(0, 256, (3, 224, 224, 3), dtype=torch.uint8, generator=g).to(DEV)
+    return m, frames, m.reference_logits(frames)
+
+
+@pytest.mark.parametrize("flags", [
+    {},                                                                     # the benchmarked path
+    {"mall_chunk": 1},                                                      # stage 1 on batch-slice views
+    {"stem_u8": False, "bneck": False, "mall_chunk": 1},                    # preprocess + stem_pool, patch / chain
+    {"stem_u8": False, "fuse_stem_pool": False, "bneck": False, "chain": False, "exp3": False},   # one conv per launch
+], ids=["default", "chunked", "chained", "unfused"])
+def test_resnet50_on_guarded_workspace(resnet, monkeypatch, flags):
+    m, frames, ref = resnet
+    for k, v in flags.items():
+        monkeypatch.setattr(m, k, v)
+    m.release_workspace()
+    plain = m.logits(frames).clone()
+    torch.cuda.synchronize()
+    checks = _guard_workspace(m, monkeypatch)
+    guard = m.logits(frames)
+    torch.cuda.synchronize()
+    assert len(checks) > 4
+    for c in checks:
+        c()
+    assert torch.isfinite(guard.float()).all()
+    assert torch.equal(_bits(guard), _bits(plain))
+    cos = F.cosine_similarity(plain.float(), ref, dim=1)
+    assert cos.min().item() > 0.995, cos
+
+
+@pytest.mark.parametrize("decode", [False, True])
+def test_yolov8n_on_guarded_workspace(native, monkeypatch, decode):
+    """YOLOv8-n's conv side (stem to head outputs, or to decoded boxes / scores / classes) on one
+    480 x 640 frame; the upsampled half of l15's input buffer is never written and stays poison."""
+    from aiko_services_amd.models import yolov8 as Y
+    m = Y.YOLOv8("n", device=DEV, cls_bias=0.0)
+    assert not decode or m._decode_fused_ok()
+    g = torch.Generator().manual_seed(12)
+    frames = torch.randint(0, 256, (1, 480, 640, 3), generator=g, dtype=torch.uint8).to(DEV)
+
+    def run():
+        if decode:
+            return m.head_outputs(None, a0=m.stem_from_frames(frames), decode=True)
+        return m.head_outputs(m.preprocess(frames))
+
+    plain = [t.clone() for t in run()]
+    torch.cuda.synchronize()
+    checks = _guard_workspace(m, monkeypatch)
+    guard = run()
+    torch.cuda.synchronize()
+    assert len(checks) > 10
+    for c in checks:
+        c()
+    for p, t in zip(plain, guard):
+        if t.dtype.is_floating_point:
+            assert torch.isfinite(t.float()).all()
+        assert torch.equal(_bits(p), _bits(t))
+    if not decode:
+        for o, r in zip(plain, m.reference_head_outputs(frames)):         # the bound of test_gpu_detect
+            cos = F.cosine_similarity(_nchw(o).float().flatten(), r.flatten(), dim=0).item()
+            assert cos > 0.99, cos
+    else:
+        from aiko_services_amd.ops import detect as DT
+        feats = m.head_outputs(None, a0=m.stem_from_frames(frames))
+        A = sum(f.shape[1] * f.shape[2] for f in feats)
+        bd, sd, cd = DT.yolo_decode(feats, Y.STRIDES, m.nc_pad, boxes=torch.empty(1, A, 4, device=DEV),
+                                    scores=torch.empty(1, A, device=DEV),
+                                    cls=torch.empty(1, A, dtype=torch.int32, device=DEV))
+        torch.cuda.synchronize()
+        assert torch.equal(plain[2], cd) and torch.equal(plain[1], sd)
+        assert (plain[0] - bd).abs().max().item() < 1e-3 * bd.abs().max().item()
