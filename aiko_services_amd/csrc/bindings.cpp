@@ -68,6 +68,8 @@ int aiko_conv_chain(const void* A, const void* W1, const float* b1, const void* 
 int aiko_maxpool(const void* x, void* y, int B, int H, int W, int C, int Ho, int Wo, int k,
                  int s, int p, int ldx, int ldy, hipStream_t stream);
 int aiko_resize_u8(const void* in, void* out, int B, int Hin, int Win, int Ho, int Wo, hipStream_t stream);
+int aiko_roi_crop_u8(const void* frames, const float* det, const int* count, void* crops, int* rois, int B, int H,
+                     int W, int max_det, int K, int Ho, int Wo, float margin, hipStream_t stream);
 int aiko_batchnorm(const void* x, void* y, const float* scale, const float* shift, long P, int C, int ldx,
                    int ldy, int act, hipStream_t stream);
 int aiko_upsample2x(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy,
@@ -870,6 +872,46 @@ void resize_u8_out(const at::Tensor& x, at::Tensor& y) {
                "resize_u8");
 }
 
+// crops[b*k + i] <- the rect of det[b, i] (i < min(count[b], k), coordinates finite) resized to
+// crops' [Ho, Wo]; rois[b*k + i] <- that rect (x0, y0, x1, y1), half-open; other slots zero
+void roi_crop_out(const at::Tensor& frames, const at::Tensor& det, const at::Tensor& count, int64_t k,
+                  double margin, at::Tensor& crops, at::Tensor& rois) {
+  check_cuda(frames, "frames");
+  check_cuda(det, "det");
+  check_cuda(count, "count");
+  check_cuda(crops, "crops");
+  check_cuda(rois, "rois");
+  TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 4 && frames.size(3) == 3 &&
+                  frames.is_contiguous() && frames.numel() >= 4,
+              "aiko.roi_crop_out: frames uint8 [B, H, W, 3] contiguous required");
+  const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2);
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(0) == B && det.size(2) == 6 &&
+                  det.is_contiguous(),
+              "aiko.roi_crop_out: det fp32 [B, max_det, 6] contiguous required");
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 && count.size(0) == B && count.is_contiguous(),
+              "aiko.roi_crop_out: count int32 [B] required");
+  const int64_t max_det = det.size(1);
+  TORCH_CHECK(k >= 1 && k <= max_det, "aiko.roi_crop_out: 1 <= k <= max_det (", max_det, ") required, got ", k);
+  TORCH_CHECK(margin >= 0.0 && margin <= 3.0e38, "aiko.roi_crop_out: a finite margin >= 0 required");
+  TORCH_CHECK(B * k <= 65535, "aiko.roi_crop_out: B * k = ", B * k, " ROI slots exceed the grid limit (65535)");
+  TORCH_CHECK(crops.scalar_type() == at::kByte && crops.dim() == 4 && crops.size(0) == B * k && crops.size(3) == 3 &&
+                  crops.is_contiguous(),
+              "aiko.roi_crop_out: crops uint8 [B*k, Ho, Wo, 3] contiguous required");
+  const int64_t Ho = crops.size(1), Wo = crops.size(2);
+  TORCH_CHECK(Ho >= 1 && Wo >= 4 && Wo % 4 == 0, "aiko.roi_crop_out: crop width must be a multiple of 4, got ", Wo);
+  TORCH_CHECK(Ho <= 16384 && Wo <= 16384 && H <= (1 << 24) && W <= (1 << 24),
+              "aiko.roi_crop_out: crop side <= 16384, frame side <= 2^24");
+  TORCH_CHECK(rois.scalar_type() == at::kInt && rois.dim() == 2 && rois.size(0) == B * k && rois.size(1) == 4 &&
+                  rois.is_contiguous(),
+              "aiko.roi_crop_out: rois int32 [B*k, 4] contiguous required");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(crops.data_ptr()) % 4 == 0 &&
+                  reinterpret_cast<uintptr_t>(rois.data_ptr()) % 16 == 0,
+              "aiko.roi_crop_out: crops 4-byte, rois 16-byte aligned");
+  check_launch(aiko_roi_crop_u8(frames.data_ptr(), det.data_ptr<float>(), count.data_ptr<int>(), crops.data_ptr(),
+                                rois.data_ptr<int>(), B, H, W, max_det, k, Ho, Wo, (float)margin, cur_stream()),
+               "roi_crop_u8");
+}
+
 void batchnorm_out(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift, at::Tensor& y, int64_t act) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -1464,6 +1506,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("preprocess_out(Tensor frames, Tensor(a!) out, int Ho, int Wo, int pad_t, int pad_l, float[] mean, float[] std, bool bgr, float[] canvas=[]) -> ()");
   m.def("upsample2x_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("resize_u8_out(Tensor x, Tensor(a!) y) -> ()");
+  m.def("roi_crop_out(Tensor frames, Tensor det, Tensor count, int k, float margin, Tensor(a!) crops, Tensor(b!) rois) -> ()");
   m.def("batchnorm_out(Tensor x, Tensor scale, Tensor shift, Tensor(a!) y, int act) -> ()");
   m.def("yolo_decode_out(Tensor[] feats, int[] strides, int nc, int reg_max, Tensor(a!) boxes, Tensor(b!) scores, Tensor(c!) cls) -> ()");
   m.def("topk_nms_out(Tensor boxes, Tensor scores, Tensor cls, int max_cand, float[] params, Tensor(a!) det, Tensor(b!) count) -> ()");
@@ -1511,6 +1554,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("stem_direct_out", &stem_direct_out);
   m.impl("upsample2x_out", &upsample2x_out);
   m.impl("resize_u8_out", &resize_u8_out);
+  m.impl("roi_crop_out", &roi_crop_out);
   m.impl("batchnorm_out", &batchnorm_out);
   m.impl("yolo_decode_out", &yolo_decode_out);
   m.impl("topk_nms_out", &topk_nms_out);

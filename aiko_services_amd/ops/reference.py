@@ -119,3 +119,46 @@ def nms_ref(boxes, scores, cls, conf=0.25, iou=0.7, max_candidates=1024, max_det
             break
         removed |= m[i] & (torch.arange(idx.numel()) > i)
     return idx[torch.tensor(keep, dtype=torch.long, device=boxes.device)]
+
+
+# ---- ROI crop -------------------------------------------------------------------------------
+
+def roi_rects_ref(det: torch.Tensor, count: torch.Tensor, k: int, hw, margin: float = 0.0) -> torch.Tensor:
+    """Rects of ``ops.roi.roi_crop``: int32 ``[B*k, 4]`` = (X0, Y0, X1, Y1), half-open, zero for a
+    slot that is not used.  fp32 throughout, one rounding per operation in the kernel's order
+    (``margin`` is a float32 scalar), so the kernel's rects equal these bit for bit.  CPU or GPU."""
+    H, W = int(hw[0]), int(hw[1])
+    B = det.shape[0]
+    d = det[:, :k, :4].to(torch.float32)
+    x1, y1, x2, y2 = d.unbind(-1)
+    m = torch.tensor(float(margin), dtype=torch.float32, device=det.device)
+    bw, bh = x2 - x1, y2 - y1
+    ex, ey = m * bw, m * bh
+    fx0, fx1 = torch.floor(x1 - ex), torch.ceil(x2 + ex)
+    fy0, fy1 = torch.floor(y1 - ey), torch.ceil(y2 + ey)
+    X0 = fx0.clamp(0, W - 1)
+    X1 = torch.maximum(fx1, X0 + 1).clamp(max=W)
+    Y0 = fy0.clamp(0, H - 1)
+    Y1 = torch.maximum(fy1, Y0 + 1).clamp(max=H)
+    n = count.to(torch.int64).clamp(0, k)
+    valid = (torch.arange(k, device=det.device)[None, :] < n[:, None]) & torch.isfinite(d).all(-1)
+    rect = torch.stack([X0, Y0, X1, Y1], -1)
+    rect = torch.where(valid[..., None], rect, torch.zeros_like(rect))     # drops the NaNs of unused rows
+    return rect.to(torch.int32).reshape(B * k, 4)
+
+
+def roi_crop_ref(frames: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k: int, size=(224, 224),
+                 margin: float = 0.0):
+    """``ops.roi.roi_crop`` with torch: one bilinear ``F.interpolate`` (half-pixel centres) per
+    rect of :func:`roi_rects_ref`, rounded and clamped to uint8; unused slots are zeros.  Returns
+    (crops uint8 ``[B*k, Ho, Wo, 3]``, rois int32 ``[B*k, 4]``)."""
+    B, H, W, _ = frames.shape
+    rois = roi_rects_ref(det, count, k, (H, W), margin)
+    crops = torch.zeros(B * k, size[0], size[1], 3, dtype=torch.uint8, device=frames.device)
+    for slot, (X0, Y0, X1, Y1) in enumerate(rois.tolist()):
+        if X1 <= X0:
+            continue
+        sub = frames[slot // k, Y0:Y1, X0:X1].permute(2, 0, 1)[None].float()
+        out = F.interpolate(sub, size=tuple(size), mode="bilinear", align_corners=False)
+        crops[slot] = out.round().clamp(0, 255)[0].permute(1, 2, 0).to(torch.uint8)
+    return crops, rois
