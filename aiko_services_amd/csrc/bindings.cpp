@@ -70,6 +70,10 @@ int aiko_maxpool(const void* x, void* y, int B, int H, int W, int C, int Ho, int
 int aiko_resize_u8(const void* in, void* out, int B, int Hin, int Win, int Ho, int Wo, hipStream_t stream);
 int aiko_roi_crop_u8(const void* frames, const float* det, const int* count, void* crops, int* rois, int B, int H,
                      int W, int max_det, int K, int Ho, int Wo, float margin, hipStream_t stream);
+int aiko_draw_detections(const void* frames, void* out, const float* det, const int* count, const int* labels,
+                         const float* scores, const void* names, const void* font, const void* palette, int B, int H,
+                         int W, int max_det, int K, int C, int L, int G, int gh, int gw, int P, int t, int s,
+                         float margin, int show_score, hipStream_t stream);
 int aiko_batchnorm(const void* x, void* y, const float* scale, const float* shift, long P, int C, int ldx,
                    int ldy, int act, hipStream_t stream);
 int aiko_upsample2x(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy,
@@ -912,6 +916,80 @@ void roi_crop_out(const at::Tensor& frames, const at::Tensor& det, const at::Ten
                "roi_crop_u8");
 }
 
+// out <- frames with the boxes and labels of det[b, i] (i < min(count[b], k), coordinates finite)
+// drawn over them; slot b*k + i of labels / scores overrides the detector's class / score.  out may
+// be frames itself (drawn in place)
+void draw_detections_out(const at::Tensor& frames, const at::Tensor& det, const at::Tensor& count, int64_t k,
+                         const c10::optional<at::Tensor>& labels, const c10::optional<at::Tensor>& scores,
+                         const at::Tensor& names, const at::Tensor& font, const at::Tensor& palette,
+                         int64_t glyph_width, int64_t thickness, int64_t text_scale, double margin, bool show_score,
+                         at::Tensor& out) {
+  check_cuda(frames, "frames");
+  check_cuda(det, "det");
+  check_cuda(count, "count");
+  check_cuda(names, "names");
+  check_cuda(font, "font");
+  check_cuda(palette, "palette");
+  check_cuda(out, "out");
+  TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 4 && frames.size(3) == 3 &&
+                  frames.is_contiguous() && frames.numel() >= 3,
+              "aiko.draw_detections_out: frames uint8 [B, H, W, 3] contiguous required");
+  const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2);
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(0) == B && det.size(2) == 6 &&
+                  det.is_contiguous(),
+              "aiko.draw_detections_out: det fp32 [B, max_det, 6] contiguous required");
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 && count.size(0) == B && count.is_contiguous(),
+              "aiko.draw_detections_out: count int32 [B] required");
+  const int64_t max_det = det.size(1);
+  TORCH_CHECK(k >= 1 && k <= max_det, "aiko.draw_detections_out: 1 <= k <= max_det (", max_det, ") required, got ", k);
+  const int* lp = nullptr;
+  const float* sp = nullptr;
+  if (labels.has_value()) {
+    check_cuda(*labels, "labels");
+    TORCH_CHECK(labels->scalar_type() == at::kInt && labels->dim() == 1 && labels->size(0) == B * k &&
+                    labels->is_contiguous(),
+                "aiko.draw_detections_out: labels int32 [B*k] required");
+    lp = labels->data_ptr<int>();
+  }
+  if (scores.has_value()) {
+    check_cuda(*scores, "scores");
+    TORCH_CHECK(scores->scalar_type() == at::kFloat && scores->dim() == 1 && scores->size(0) == B * k &&
+                    scores->is_contiguous(),
+                "aiko.draw_detections_out: scores fp32 [B*k] required");
+    sp = scores->data_ptr<float>();
+  }
+  TORCH_CHECK(names.scalar_type() == at::kByte && names.dim() == 2 && names.is_contiguous() && names.size(1) >= 1 &&
+                  names.size(1) <= 32 && names.size(0) < (1 << 24),
+              "aiko.draw_detections_out: names uint8 [C, L] contiguous with 1 <= L <= 32 required");
+  TORCH_CHECK(font.scalar_type() == at::kByte && font.dim() == 2 && font.is_contiguous() && font.size(1) >= 1 &&
+                  font.size(1) <= 16 && font.size(0) < (1 << 24),
+              "aiko.draw_detections_out: font uint8 [G, gh] contiguous with 1 <= gh <= 16 required");
+  TORCH_CHECK(glyph_width >= 1 && glyph_width <= 8, "aiko.draw_detections_out: 1 <= glyph_width <= 8 required, got ",
+              glyph_width);
+  TORCH_CHECK(palette.scalar_type() == at::kByte && palette.dim() == 2 && palette.size(1) == 3 &&
+                  palette.is_contiguous() && palette.size(0) >= 1 && palette.size(0) < (1 << 24),
+              "aiko.draw_detections_out: palette uint8 [P, 3] contiguous with P >= 1 required");
+  TORCH_CHECK(thickness >= 1 && thickness <= 16, "aiko.draw_detections_out: 1 <= thickness <= 16 required, got ",
+              thickness);
+  TORCH_CHECK(text_scale >= 1 && text_scale <= 4, "aiko.draw_detections_out: 1 <= text_scale <= 4 required, got ",
+              text_scale);
+  TORCH_CHECK(margin >= 0.0 && margin <= 3.0e38, "aiko.draw_detections_out: a finite margin >= 0 required");
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.sizes() == frames.sizes() && out.is_contiguous(),
+              "aiko.draw_detections_out: out uint8 [B, H, W, 3] contiguous, the shape of frames, required");
+  const auto fp = reinterpret_cast<uintptr_t>(frames.data_ptr()), op = reinterpret_cast<uintptr_t>(out.data_ptr());
+  const uintptr_t nbytes = (uintptr_t)frames.numel();
+  TORCH_CHECK(fp == op || fp + nbytes <= op || op + nbytes <= fp,
+              "aiko.draw_detections_out: out overlaps frames without being the same tensor");
+  TORCH_CHECK(B <= 65535 && (H + 31) / 32 <= 65535 && H <= (1 << 24) && W <= (1 << 24),
+              "aiko.draw_detections_out: B = ", B, ", H = ", H, ", W = ", W,
+              " exceed the grid limit (65535 frames, 65535 tile rows of 32, side <= 2^24)");
+  check_launch(aiko_draw_detections(frames.data_ptr(), out.data_ptr(), det.data_ptr<float>(), count.data_ptr<int>(), lp,
+                                    sp, names.data_ptr(), font.data_ptr(), palette.data_ptr(), B, H, W, max_det, k,
+                                    names.size(0), names.size(1), font.size(0), font.size(1), glyph_width,
+                                    palette.size(0), thickness, text_scale, (float)margin, show_score, cur_stream()),
+               "draw_detections");
+}
+
 void batchnorm_out(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift, at::Tensor& y, int64_t act) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -1507,6 +1585,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("upsample2x_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("resize_u8_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("roi_crop_out(Tensor frames, Tensor det, Tensor count, int k, float margin, Tensor(a!) crops, Tensor(b!) rois) -> ()");
+  m.def("draw_detections_out(Tensor frames, Tensor det, Tensor count, int k, Tensor? labels, Tensor? scores, Tensor names, Tensor font, Tensor palette, int glyph_width, int thickness, int text_scale, float margin, bool show_score, Tensor(a!) out) -> ()");
   m.def("batchnorm_out(Tensor x, Tensor scale, Tensor shift, Tensor(a!) y, int act) -> ()");
   m.def("yolo_decode_out(Tensor[] feats, int[] strides, int nc, int reg_max, Tensor(a!) boxes, Tensor(b!) scores, Tensor(c!) cls) -> ()");
   m.def("topk_nms_out(Tensor boxes, Tensor scores, Tensor cls, int max_cand, float[] params, Tensor(a!) det, Tensor(b!) count) -> ()");
@@ -1555,6 +1634,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("upsample2x_out", &upsample2x_out);
   m.impl("resize_u8_out", &resize_u8_out);
   m.impl("roi_crop_out", &roi_crop_out);
+  m.impl("draw_detections_out", &draw_detections_out);
   m.impl("batchnorm_out", &batchnorm_out);
   m.impl("yolo_decode_out", &yolo_decode_out);
   m.impl("topk_nms_out", &topk_nms_out);

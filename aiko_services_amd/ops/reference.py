@@ -162,3 +162,78 @@ def roi_crop_ref(frames: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k
         out = F.interpolate(sub, size=tuple(size), mode="bilinear", align_corners=False)
         crops[slot] = out.round().clamp(0, 255)[0].permute(1, 2, 0).to(torch.uint8)
     return crops, rois
+
+
+# ---- detection overlay ----------------------------------------------------------------------
+
+def overlay_text_ref(c: int, p: torch.Tensor, names: torch.Tensor, show_score: bool) -> list[int]:
+    """Character codes of one label: the bytes of ``names[c]`` up to the first zero (none if ``c``
+    is outside the table), then — if ``show_score`` — a space (only after a name) and the two
+    digits of ``min(max(rint(p * 100), 0), 99)``, the product in fp32, NaN counting as 0."""
+    text = []
+    if 0 <= c < names.shape[0]:
+        for ch in names[c].tolist():
+            if ch == 0:
+                break
+            text.append(ch)
+    if show_score:
+        v = torch.round(p.to(torch.float32) * 100.0)            # fp32 product, round half to even
+        pct = 0 if bool(torch.isnan(v)) else int(min(max(float(v), 0.0), 99.0))
+        text += ([32] if text else []) + [48 + pct // 10, 48 + pct % 10]
+    return text
+
+
+def draw_detections_ref(frames: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k: int, names: torch.Tensor,
+                        font: torch.Tensor, palette: torch.Tensor, *, labels: torch.Tensor | None = None,
+                        scores: torch.Tensor | None = None, thickness: int = 2, text_scale: int = 1,
+                        margin: float = 0.0, show_score: bool = True, glyph_width: int | None = None) -> torch.Tensor:
+    """``ops.overlay.draw_detections`` with torch on the CPU, painter's style: per frame the used
+    rows (rects of :func:`roi_rects_ref`) are painted from the highest index down to 0, each as
+    four outline strips and then its label block, so the lowest index ends on top and a label
+    covers its own outline.  Returns a new uint8 ``[B, H, W, 3]`` tensor."""
+    frames, det, count = frames.cpu(), det.cpu().to(torch.float32), count.cpu()
+    names, font, palette = names.cpu(), font.cpu(), palette.cpu()
+    B, H, W, _ = frames.shape
+    G, gh = font.shape
+    gw = 6 if glyph_width is None else int(glyph_width)
+    s, t = int(text_scale), int(thickness)
+    cw, ch = gw * s, gh * s
+    out = frames.clone()
+    rects = roi_rects_ref(det, count, k, (H, W), margin).view(B, k, 4).tolist()
+    # every glyph as a [ch, cw] mask: bit 7 of a row byte is the leftmost pixel
+    shifts = 7 - torch.arange(gw)
+    masks = ((font.to(torch.int64)[:, :, None] >> shifts[None, None, :]) & 1).bool()
+    masks = masks.repeat_interleave(s, 1).repeat_interleave(s, 2)
+    for b in range(B):
+        for i in reversed(range(k)):
+            X0, Y0, X1, Y1 = rects[b][i]
+            if X1 <= X0:
+                continue
+            slot = b * k + i
+            if labels is not None:
+                c = int(labels[slot])
+            else:
+                cf = float(det[b, i, 5])
+                c = 0 if cf != cf else int(min(max(cf, -2.0 ** 31), 2.0 ** 31 - 1))
+            p = scores[slot].cpu() if scores is not None else det[b, i, 4]
+            col = palette[c % palette.shape[0] if c >= 0 else 0]
+            R, Gc, Bc = (int(v) for v in col)
+            ink = 0 if 299 * R + 587 * Gc + 114 * Bc >= 128000 else 255
+            frame = out[b]
+            frame[Y0:min(Y0 + t, Y1), X0:X1] = col
+            frame[max(Y1 - t, Y0):Y1, X0:X1] = col
+            frame[Y0:Y1, X0:min(X0 + t, X1)] = col
+            frame[Y0:Y1, max(X1 - t, X0):X1] = col
+            text = overlay_text_ref(c, p, names, show_score)
+            if not text:
+                continue
+            Lw, Lh = len(text) * cw + 2 * s, ch + 2 * s
+            lx = max(min(X0, W - Lw), 0)
+            ly = Y0 - Lh if Y0 - Lh >= 0 else Y0
+            block = col.expand(Lh, Lw, 3).clone()
+            for j, code in enumerate(text):
+                if 32 <= code < 32 + G:
+                    block[s:s + ch, s + j * cw:s + (j + 1) * cw][masks[code - 32]] = ink
+            hh, ww = min(Lh, H - ly), min(Lw, W - lx)
+            frame[ly:ly + hh, lx:lx + ww] = block[:hh, :ww]
+    return out
