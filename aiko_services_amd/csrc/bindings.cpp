@@ -11,6 +11,7 @@
 #include <hip/hip_runtime.h>
 
 #include <climits>
+#include <cmath>
 #include <vector>
 
 extern "C" {
@@ -74,6 +75,8 @@ int aiko_draw_detections(const void* frames, void* out, const float* det, const 
                          const float* scores, const void* names, const void* font, const void* palette, int B, int H,
                          int W, int max_det, int K, int C, int L, int G, int gh, int gw, int P, int t, int s,
                          float margin, int show_score, hipStream_t stream);
+int aiko_yuv_to_rgb_u8(const void* raw, void* out, int B, int H, int W, int fmt, const float* coef, int half,
+                       hipStream_t stream);
 int aiko_batchnorm(const void* x, void* y, const float* scale, const float* shift, long P, int C, int ldx,
                    int ldy, int act, hipStream_t stream);
 int aiko_upsample2x(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy,
@@ -990,6 +993,44 @@ void draw_detections_out(const at::Tensor& frames, const at::Tensor& det, const 
                "draw_detections");
 }
 
+// out [B, H, W, 3] <- raw [B, frame_bytes] YUV frames, tightly packed.  format: 0 nv12, 1 i420,
+// 2 i444, 3 yuyv; coeffs: yoff, ygain, rv, gu, gv, bu; round_mode: 0 rint, 1 add half and truncate
+void yuv_to_rgb_out(const at::Tensor& raw, int64_t height, int64_t width, int64_t format,
+                    at::ArrayRef<double> coeffs, int64_t round_mode, at::Tensor& out) {
+  check_cuda(raw, "raw");
+  check_cuda(out, "out");
+  TORCH_CHECK(raw.device() == out.device(), "aiko.yuv_to_rgb_out: raw and out on different devices");
+  TORCH_CHECK(format >= 0 && format <= 3, "aiko.yuv_to_rgb_out: unknown format code ", format);
+  TORCH_CHECK(round_mode == 0 || round_mode == 1, "aiko.yuv_to_rgb_out: unknown round mode ", round_mode);
+  TORCH_CHECK(coeffs.size() == 6, "aiko.yuv_to_rgb_out: 6 coefficients (yoff, ygain, rv, gu, gv, bu) required, got ",
+              coeffs.size());
+  float coef[6];
+  for (int i = 0; i < 6; ++i) {
+    coef[i] = (float)coeffs[i];
+    TORCH_CHECK(std::isfinite(coef[i]), "aiko.yuv_to_rgb_out: coefficient ", i, " is not finite in fp32");
+  }
+  TORCH_CHECK(height >= 1 && width >= 1 && height <= 32768 && width <= 32768,
+              "aiko.yuv_to_rgb_out: 1 <= height, width <= 32768 required, got ", height, " x ", width);
+  TORCH_CHECK(format != 3 || width % 2 == 0, "aiko.yuv_to_rgb_out: yuyv needs an even width, got ", width);
+  const int64_t H = height, W = width, cplane = ((H + 1) / 2) * ((W + 1) / 2);
+  const int64_t frame_bytes = format == 2 ? 3 * H * W : format == 3 ? 2 * H * W : H * W + 2 * cplane;
+  TORCH_CHECK(raw.scalar_type() == at::kByte && raw.dim() == 2 && raw.is_contiguous() && raw.size(0) >= 1,
+              "aiko.yuv_to_rgb_out: raw uint8 [B, frame_bytes] contiguous required");
+  TORCH_CHECK(raw.size(1) == frame_bytes, "aiko.yuv_to_rgb_out: a ", H, " x ", W, " frame of this format has ",
+              frame_bytes, " bytes, raw has ", raw.size(1));
+  const int64_t B = raw.size(0);
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.dim() == 4 && out.size(0) == B && out.size(1) == H &&
+                  out.size(2) == W && out.size(3) == 3 && out.is_contiguous(),
+              "aiko.yuv_to_rgb_out: out uint8 [B, H, W, 3] contiguous required");
+  TORCH_CHECK(B <= 65535, "aiko.yuv_to_rgb_out: B = ", B, " exceeds the grid limit (65535 frames)");
+  const auto rp = reinterpret_cast<uintptr_t>(raw.data_ptr()), op = reinterpret_cast<uintptr_t>(out.data_ptr());
+  TORCH_CHECK(rp + (uintptr_t)raw.numel() <= op || op + (uintptr_t)out.numel() <= rp,
+              "aiko.yuv_to_rgb_out: raw and out overlap");
+  check_launch(aiko_yuv_to_rgb_u8(raw.data_ptr(), out.data_ptr(), B, H, W, (int)format, coef, (int)round_mode,
+                                  cur_stream()),
+               "yuv_to_rgb_u8");
+}
+
 void batchnorm_out(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift, at::Tensor& y, int64_t act) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -1586,6 +1627,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("resize_u8_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("roi_crop_out(Tensor frames, Tensor det, Tensor count, int k, float margin, Tensor(a!) crops, Tensor(b!) rois) -> ()");
   m.def("draw_detections_out(Tensor frames, Tensor det, Tensor count, int k, Tensor? labels, Tensor? scores, Tensor names, Tensor font, Tensor palette, int glyph_width, int thickness, int text_scale, float margin, bool show_score, Tensor(a!) out) -> ()");
+  m.def("yuv_to_rgb_out(Tensor raw, int height, int width, int format, float[] coeffs, int round_mode, Tensor(a!) out) -> ()");
   m.def("batchnorm_out(Tensor x, Tensor scale, Tensor shift, Tensor(a!) y, int act) -> ()");
   m.def("yolo_decode_out(Tensor[] feats, int[] strides, int nc, int reg_max, Tensor(a!) boxes, Tensor(b!) scores, Tensor(c!) cls) -> ()");
   m.def("topk_nms_out(Tensor boxes, Tensor scores, Tensor cls, int max_cand, float[] params, Tensor(a!) det, Tensor(b!) count) -> ()");
@@ -1635,6 +1677,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("resize_u8_out", &resize_u8_out);
   m.impl("roi_crop_out", &roi_crop_out);
   m.impl("draw_detections_out", &draw_detections_out);
+  m.impl("yuv_to_rgb_out", &yuv_to_rgb_out);
   m.impl("batchnorm_out", &batchnorm_out);
   m.impl("yolo_decode_out", &yolo_decode_out);
   m.impl("topk_nms_out", &topk_nms_out);

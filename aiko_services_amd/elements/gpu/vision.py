@@ -7,7 +7,9 @@
   ``height`` x ``width`` produced directly in HBM (a rotating pool of ``pool`` random batches,
   like a hardware decoder writing into device memory; no host upload on the hot path).  In a
   stream it can also run as a frame generator (``frames``, ``rate``).  With ``global: true``
-  only rank ``src`` produces frames — ``world x batch`` of them — for a FrameFanout.
+  only rank ``src`` produces frames — ``world x batch`` of them — for a FrameFanout.  With
+  ``format: nv12 | i420 | i444 | yuyv`` the slots hold raw ``[batch, frame_bytes]`` frames, what a
+  decoder really writes, for a ``YuvToRgb`` (``ingest.py``); ``FrameUpload`` takes the same parameter.
 * ``FrameUpload`` — host frames (a decoder / camera / file reader in host memory, or
   ``SyntheticFrames`` with ``host: true``) -> a FramePool slot in HBM: pinned staging, the
   H2D copy on the element's own copy stream (it overlaps the previous frames' compute), the
@@ -61,6 +63,16 @@ class SyntheticFrames(GpuPipelineElement):
         # frame's pixels — and every output computed from them — depend on the frame id alone,
         # not on which slot it was served from
         self._stamp = str(self.get_parameter("stamp", False)[0]).lower() in ("true", "1", "yes")
+        # ``format``: "rgb" (default) fills [B, H, W, 3] pixels; a raw format of ``ops.yuv`` (nv12,
+        # i420, i444, yuyv) makes the slots [B, frame_bytes] of random bytes — every byte pattern
+        # is valid YUV — as a hardware decoder writes them, for a ``YuvToRgb`` to convert
+        self._format = str(self.get_parameter("format", "rgb")[0]).lower()
+
+    def _batch_shape(self, B, H, W):
+        if self._format == "rgb":
+            return (B, H, W, 3)
+        from ...ops.yuv import frame_bytes
+        return (B, frame_bytes(self._format, H, W))
 
     def _ensure_pool(self, glob):
         if self.frame_pool is not None:
@@ -79,8 +91,9 @@ class SyntheticFrames(GpuPipelineElement):
         W = _int(self.get_parameter("width", 224)[0], 224)
         n = max(1, _int(self.get_parameter("pool", 2)[0], 2))
         seed = _int(self.get_parameter("seed", 0)[0], 0)
-        self._shape = (B, H, W, 3)
-        self.frame_pool = FramePool(n, B * H * W * 3, device=self.device)
+        self._shape = self._batch_shape(B, H, W)
+        self.frame_pool = FramePool(n, B * (self._shape[1] if len(self._shape) == 2 else H * W * 3),
+                                    device=self.device)
         g = torch.Generator(device=self.device).manual_seed(seed)
         slots = [self.frame_pool.acquire(0) for _ in range(n)]
         same = None
@@ -103,8 +116,9 @@ class SyntheticFrames(GpuPipelineElement):
             n = max(1, _int(self.get_parameter("pool", 2)[0], 2))
             g = torch.Generator().manual_seed(_int(self.get_parameter("seed", 0)[0], 0))
             pin = torch.cuda.is_available()
-            self.host_pool = [torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, generator=g).pin_memory()
-                               if pin else torch.randint(0, 256, (B, H, W, 3), dtype=torch.uint8, generator=g)
+            shape = self._batch_shape(B, H, W)
+            self.host_pool = [torch.randint(0, 256, shape, dtype=torch.uint8, generator=g).pin_memory()
+                               if pin else torch.randint(0, 256, shape, dtype=torch.uint8, generator=g)
                                for _ in range(n)]
             self._next = 0
         frames = self.host_pool[self._next]
@@ -181,7 +195,15 @@ class FrameUpload(GpuPipelineElement):
     stream into a FramePool slot (``pool`` slots of the batch's size), the frame's lane waits
     on the copy's event, and the slot is held until the frame completes — so the upload of
     frame k+1 overlaps the compute of frame k, and a hop can send the slot zero-copy
-    (``mark_frame_held``).  Output ``images``: the device batch, uint8 [B, H, W, 3]."""
+    (``mark_frame_held``).  Output ``images``: the device batch, uint8 [B, H, W, 3].
+
+    ``format`` (default ``rgb``: all of the above) may name a raw format of ``ops.yuv`` (nv12,
+    i420, i444, yuyv); ``height`` and ``width`` are then required.  ``images`` is a host uint8
+    [B, frame_bytes] tensor or array, or a list of 1-D uint8 arrays / bytes-like objects of
+    ``frame_bytes`` each (``VideoReadFile`` / ``VideoReadWebcam`` with ``raw: true``); staging,
+    copy stream, event, pool and hold are the same, the output is the raw device batch
+    [B, frame_bytes] for a ``YuvToRgb`` — which may sit behind a stage cut, so the hop carries the
+    raw slot — and ``bytes_uploaded`` counts the raw bytes: 1.5 or 2 per pixel instead of 3."""
     lane_safe = True
 
     def __init__(self, context):
@@ -195,6 +217,44 @@ class FrameUpload(GpuPipelineElement):
         self._staging = {}
         self._copy_stream = torch.cuda.Stream(device=self.device) if self.device.type == "cuda" else None
         self.bytes_uploaded = 0
+        self.format = str(self.get_parameter("format", "rgb")[0]).lower()
+        self.frame_bytes = None
+        if self.format != "rgb":
+            from ...ops.yuv import frame_bytes
+            height, width = self.get_parameter("height", None)[0], self.get_parameter("width", None)[0]
+            if height is None or width is None:
+                raise ValueError(f"FrameUpload: format {self.format} needs height and width parameters")
+            self.frame_bytes = frame_bytes(self.format, int(height), int(width))
+
+    def _as_raw_batch(self, images):
+        """Raw frames -> a uint8 [B, frame_bytes] host tensor or a list of 1-D uint8 tensors."""
+        import warnings
+
+        import numpy as np
+        n = self.frame_bytes
+
+        def one(f):
+            if not isinstance(f, (torch.Tensor, np.ndarray)):
+                f = np.frombuffer(f, dtype=np.uint8)            # bytes, bytearray, memoryview
+            if isinstance(f, np.ndarray):
+                with warnings.catch_warnings():                 # read-only (bytes, a file's buffer): only read here
+                    warnings.simplefilter("ignore", UserWarning)
+                    f = torch.from_numpy(np.ascontiguousarray(f))
+            t = f
+            if t.dtype != torch.uint8 or t.dim() != 1 or t.numel() != n:
+                raise ValueError(f"FrameUpload: a raw {self.format} frame is {n} uint8 bytes, got "
+                                 f"{t.dtype} {tuple(t.shape)}")
+            return t
+
+        if isinstance(images, (list, tuple)) and images:
+            return [one(f) for f in images]
+        if isinstance(images, np.ndarray):
+            images = torch.from_numpy(np.ascontiguousarray(images))
+        if isinstance(images, torch.Tensor) and images.dtype == torch.uint8 and images.dim() == 2 \
+                and images.shape[1] == n:
+            return images
+        raise ValueError(f"FrameUpload: raw {self.format} images must be uint8 [B, {n}] or a list of "
+                         f"{n}-byte frames")
 
     @staticmethod
     def _as_batch(images):
@@ -259,15 +319,22 @@ class FrameUpload(GpuPipelineElement):
 
     def process_frame(self, stream, images):
         from ...parallel.hop import mark_frame_held
-        batch = self._as_batch(images)
-        first = batch if isinstance(batch, torch.Tensor) else batch[0]
-        shape = (len(batch),) + tuple(first.shape[-3:]) if not isinstance(batch, torch.Tensor) else tuple(batch.shape)
-        if len(shape) != 4 or shape[3] != 3:
-            raise ValueError(f"FrameUpload: expected [B, H, W, 3] frames, got {shape}")
+        if self.frame_bytes is not None:
+            batch = self._as_raw_batch(images)
+            shape = (len(batch), self.frame_bytes)
+        else:
+            batch = self._as_batch(images)
+            first = batch if isinstance(batch, torch.Tensor) else batch[0]
+            shape = (len(batch),) + tuple(first.shape[-3:]) if not isinstance(batch, torch.Tensor) \
+                else tuple(batch.shape)
+            if len(shape) != 4 or shape[3] != 3:
+                raise ValueError(f"FrameUpload: expected [B, H, W, 3] frames, got {shape}")
         if self.device.type != "cuda":
             out = batch if isinstance(batch, torch.Tensor) else torch.stack(batch)
             return StreamEvent.OKAY, {"images": out.to(torch.uint8)}
-        nbytes = shape[0] * shape[1] * shape[2] * 3
+        nbytes = 1
+        for d in shape:
+            nbytes *= d
         pool = self._pools.get(shape)
         if pool is None:
             self._size_pool()                     # the plan's members are discovered by now

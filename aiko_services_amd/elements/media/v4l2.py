@@ -159,8 +159,10 @@ class V4L2Capture:
     def isOpened(self) -> bool:  # noqa: N802  (cv2.VideoCapture API)
         return self.fd is not None and self.streaming
 
-    def read(self):
-        """(True, RGB uint8 [H, W, 3]) for the next frame, (False, None) on timeout / error."""
+    def read(self, raw: bool = False):
+        """(True, RGB uint8 [H, W, 3]) for the next frame, (False, None) on timeout / error.
+        ``raw=True``: the frame as the camera delivered it, a copy of the YUYV buffer as a 1-D uint8
+        array of ``2 * width * height`` bytes (for ``FrameUpload`` with ``format: yuyv``)."""
         if not self.isOpened():
             return False, None
         ready, _, _ = select.select([self.fd], [], [], self.timeout_s)
@@ -172,7 +174,10 @@ class V4L2Capture:
         except OSError:
             return False, None
         try:
-            rgb = yuyv_to_rgb(self.maps[b.index][:b.bytesused], self.width, self.height)
+            if raw:
+                rgb = np.frombuffer(self.maps[b.index], dtype=np.uint8, count=self.width * self.height * 2).copy()
+            else:
+                rgb = yuyv_to_rgb(self.maps[b.index][:b.bytesused], self.width, self.height)
         finally:
             fcntl.ioctl(self.fd, VIDIOC["QBUF"], b)
         return True, rgb

@@ -52,7 +52,10 @@ def _rgb_to_yuv(rgb):
     return c(y), c(u), c(v)
 
 
-def iter_y4m(path):
+def iter_y4m(path, raw=False):
+    """RGB uint8 [H, W, 3] frames of a YUV4MPEG2 file.  ``raw=True``: no conversion — per frame
+    ``(fmt, h, w, packed)`` with ``packed`` the frame's planes as one 1-D uint8 array in the layout
+    ``ops.yuv`` names ``fmt``: ``i420`` for every ``C420*`` tag, ``i444`` for ``C444``."""
     with open(path, "rb") as f:
         header = f.readline().decode("ascii").split()
         if not header or header[0] != "YUV4MPEG2":
@@ -62,12 +65,20 @@ def iter_y4m(path):
         cs = params.get("C", "420jpeg")
         chroma444 = cs.startswith("444")
         cw, ch = (w, h) if chroma444 else ((w + 1) // 2, (h + 1) // 2)
+        if raw and cs != "444" and not cs.startswith("420"):
+            raise ValueError(f"{path}: chroma C{cs} has no raw format (C420* and C444 do)")
         while True:
             line = f.readline()
             if not line:
                 return
             if not line.startswith(b"FRAME"):
                 raise ValueError(f"{path}: corrupt frame header")
+            if raw:
+                packed = np.frombuffer(f.read(w * h + 2 * cw * ch), np.uint8)
+                if packed.size != w * h + 2 * cw * ch:
+                    raise ValueError(f"{path}: truncated frame")
+                yield ("i444" if chroma444 else "i420"), h, w, packed
+                continue
             y = np.frombuffer(f.read(w * h), np.uint8).reshape(h, w)
             u = np.frombuffer(f.read(cw * ch), np.uint8).reshape(ch, cw)
             v = np.frombuffer(f.read(cw * ch), np.uint8).reshape(ch, cw)
@@ -107,9 +118,16 @@ def write_y4m(path, frames, fps=30):
     wr.close()
 
 
-def iter_video_frames(path):
-    """RGB uint8 frames of a video file / frame directory, whatever backend is available."""
+def iter_video_frames(path, raw=False):
+    """RGB uint8 frames of a video file / frame directory, whatever backend is available.
+    ``raw=True`` (Y4M only): each frame's packed planes as a 1-D uint8 array, unconverted."""
     path = Path(path)
+    if raw:
+        if path.is_dir() or path.suffix.lower() != ".y4m":
+            raise ValueError(f"{path}: raw frames need a .y4m file")
+        for _fmt, _h, _w, packed in iter_y4m(path, raw=True):
+            yield packed
+        return
     if path.is_dir():
         from PIL import Image
         for p in sorted(path.iterdir()):
@@ -160,6 +178,9 @@ class VideoOutput(PipelineElement):
 
 
 class VideoReadFile(DataSource):
+    """Parameter ``raw: true`` (Y4M files only): ``images`` are the frames' packed planes, 1-D uint8
+    arrays, for a ``FrameUpload`` with ``format`` i420 / i444; any other file is an error."""
+
     def __init__(self, context):
         context.set_protocol("video_read_file:0")
         context.get_implementation("PipelineElement").__init__(self, context)
@@ -177,7 +198,8 @@ class VideoReadFile(DataSource):
                 except StopIteration:
                     return StreamEvent.STOP, {"diagnostic": "End of video file(s)"}
                 try:
-                    gen = iter_video_frames(path)
+                    raw = str(self.get_parameter("raw", False)[0]).lower() in ("true", "1", "yes")
+                    gen = iter_video_frames(path, raw=raw)
                 except ValueError as exc:
                     return StreamEvent.ERROR, {"diagnostic": str(exc)}
                 stream.variables["video_frame_generator"] = gen

@@ -25,10 +25,11 @@ except ImportError:
 __all__ = ["VideoReadWebcam", "open_camera", "postprocess_frame"]
 
 
-def open_camera(path, width: int = 640, height: int = 480):
+def open_camera(path, width: int = 640, height: int = 480, raw: bool = False):
     """A ``cv2.VideoCapture``-like reader for ``path`` (``/dev/videoN`` or N) whose ``read()``
-    returns RGB frames; OpenCV when available (its BGR converted), else V4L2."""
-    if _CV2:
+    returns RGB frames; OpenCV when available (its BGR converted), else V4L2.  ``raw``: always
+    V4L2, whose ``read(raw=True)`` hands out the camera's YUYV buffer unconverted."""
+    if _CV2 and not raw:
         cap = cv2.VideoCapture(path)
         if not cap.isOpened():
             raise OSError(f"cannot open camera {path}")
@@ -62,7 +63,9 @@ def postprocess_frame(rgb: np.ndarray, color=True, flip="none") -> np.ndarray:
 
 
 class VideoReadWebcam(DataSource):
-    """Camera source with EC-tunable ``color``, ``flip``, ``path``."""
+    """Camera source with EC-tunable ``color``, ``flip``, ``path``.  Parameter ``raw: true``:
+    ``images`` are the camera's YUYV buffers (1-D uint8 arrays of ``2 * width * height`` bytes,
+    ``color`` / ``flip`` not applied) for a ``FrameUpload`` with ``format: yuyv``."""
 
     def __init__(self, context):
         context.set_protocol("webcam:0")
@@ -91,8 +94,9 @@ class VideoReadWebcam(DataSource):
             self.video_capture = None
         width = int(self.get_parameter("width", 640)[0])
         height = int(self.get_parameter("height", 480)[0])
+        self.raw = str(self.get_parameter("raw", False)[0]).lower() in ("true", "1", "yes")
         try:
-            self.video_capture = open_camera(path, width, height)
+            self.video_capture = open_camera(path, width, height, raw=self.raw)
         except OSError as exc:
             self.logger.error(f"Open camera: {path} failed: {exc}")
             return False
@@ -112,9 +116,11 @@ class VideoReadWebcam(DataSource):
     def frame_generator(self, stream, frame_id):
         if self.video_capture is None or not self.video_capture.isOpened():
             return StreamEvent.DROP_FRAME, {}
-        ok, rgb = self.video_capture.read()
+        ok, rgb = self.video_capture.read(raw=True) if getattr(self, "raw", False) else self.video_capture.read()
         if not ok:
             return StreamEvent.DROP_FRAME, {}
+        if getattr(self, "raw", False):
+            return StreamEvent.OKAY, {"images": [rgb]}
         if frame_id % 10 == 0:
             self.ec_producer.update("frame_id", frame_id)
         return StreamEvent.OKAY, {"images": [self.postprocess(rgb)]}

@@ -237,3 +237,50 @@ def draw_detections_ref(frames: torch.Tensor, det: torch.Tensor, count: torch.Te
             hh, ww = min(Lh, H - ly), min(Lw, W - lx)
             frame[ly:ly + hh, lx:lx + ww] = block[:hh, :ww]
     return out
+
+
+# ---- YUV ingest -----------------------------------------------------------------------------
+
+def yuv_planes_ref(raw: torch.Tensor, height: int, width: int, fmt: str):
+    """(Y, U, V) uint8 ``[B, H, W]`` of tightly packed raw frames ``[B, frame_bytes]``, the chroma
+    replicated to every pixel it serves (nearest: no interpolation)."""
+    from .yuv import frame_bytes
+    H, W = int(height), int(width)
+    raw = raw.cpu()
+    if raw.dim() != 2 or raw.dtype != torch.uint8 or raw.shape[1] != frame_bytes(fmt, H, W):
+        raise ValueError(f"yuv_planes_ref: uint8 [B, {frame_bytes(fmt, H, W)}] required, got {tuple(raw.shape)}")
+    B = raw.shape[0]
+    cw, ch = (W + 1) // 2, (H + 1) // 2
+    if fmt == "yuyv":
+        a = raw.view(B, H, W // 2, 4)
+        y = torch.stack([a[..., 0], a[..., 2]], -1).reshape(B, H, W)
+        return y, a[..., 1].repeat_interleave(2, 2), a[..., 3].repeat_interleave(2, 2)
+    y = raw[:, :H * W].view(B, H, W)
+    if fmt == "i444":
+        return y, raw[:, H * W:2 * H * W].view(B, H, W), raw[:, 2 * H * W:].view(B, H, W)
+    if fmt == "nv12":
+        c = raw[:, H * W:].view(B, ch, cw, 2)
+        u, v = c[..., 0], c[..., 1]
+    else:
+        u = raw[:, H * W:H * W + ch * cw].view(B, ch, cw)
+        v = raw[:, H * W + ch * cw:].view(B, ch, cw)
+    up = lambda p: p.repeat_interleave(2, 1).repeat_interleave(2, 2)[:, :H, :W]  # noqa: E731
+    return y, up(u), up(v)
+
+
+def yuv_to_rgb_ref(raw: torch.Tensor, height: int, width: int, fmt: str, standard: str) -> torch.Tensor:
+    """``ops.yuv.yuv_to_rgb`` with torch fp32 on the CPU, the formula of :mod:`~aiko_services_amd.ops.yuv`
+    literally: one rounding per operation, the constants as fp32 tensors from the same
+    ``STANDARDS`` row the kernel is given.  Returns uint8 ``[B, H, W, 3]``."""
+    from .yuv import STANDARDS
+    coeffs, rounding = STANDARDS[standard]
+    yoff, ygain, rv, gu, gv, bu = (torch.tensor(c, dtype=torch.float32) for c in coeffs)
+    Y, U, V = (p.to(torch.float32) for p in yuv_planes_ref(raw, height, width, fmt))
+    c = (Y - yoff) * ygain
+    u, v = U - 128.0, V - 128.0
+    rgb = torch.stack([c + rv * v, (c - gu * u) - gv * v, c + bu * u], -1)
+    if rounding == "rint":
+        rgb = torch.round(rgb).clamp_(0, 255)               # ties to even
+    else:
+        rgb = (rgb + 0.5).clamp_(0, 255)                    # the cast truncates
+    return rgb.to(torch.uint8)
