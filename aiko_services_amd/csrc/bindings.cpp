@@ -77,6 +77,8 @@ int aiko_draw_detections(const void* frames, void* out, const float* det, const 
                          float margin, int show_score, hipStream_t stream);
 int aiko_yuv_to_rgb_u8(const void* raw, void* out, int B, int H, int W, int fmt, const float* coef, int half,
                        hipStream_t stream);
+int aiko_rgb_to_yuv_u8(const void* rgb, void* out, int B, int H, int W, int fmt, const float* coef, int half,
+                       hipStream_t stream);
 int aiko_batchnorm(const void* x, void* y, const float* scale, const float* shift, long P, int C, int ldx,
                    int ldy, int act, hipStream_t stream);
 int aiko_upsample2x(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy,
@@ -1031,6 +1033,46 @@ void yuv_to_rgb_out(const at::Tensor& raw, int64_t height, int64_t width, int64_
                "yuv_to_rgb_u8");
 }
 
+// out [B, frame_bytes] YUV frames, tightly packed <- rgb [B, H, W, 3].  format: 0 nv12, 1 i420,
+// 2 i444, 3 yuyv; coeffs: yoff, yr, yg, yb, ur, ug, ub, vr, vg, vb; round_mode: 0 rint, 1 add half
+// and truncate
+void rgb_to_yuv_out(const at::Tensor& rgb, int64_t format, at::ArrayRef<double> coeffs, int64_t round_mode,
+                    at::Tensor& out) {
+  check_cuda(rgb, "rgb");
+  check_cuda(out, "out");
+  TORCH_CHECK(rgb.device() == out.device(), "aiko.rgb_to_yuv_out: rgb and out on different devices");
+  TORCH_CHECK(format >= 0 && format <= 3, "aiko.rgb_to_yuv_out: unknown format code ", format);
+  TORCH_CHECK(round_mode == 0 || round_mode == 1, "aiko.rgb_to_yuv_out: unknown round mode ", round_mode);
+  TORCH_CHECK(coeffs.size() == 10,
+              "aiko.rgb_to_yuv_out: 10 coefficients (yoff, yr, yg, yb, ur, ug, ub, vr, vg, vb) required, got ",
+              coeffs.size());
+  float coef[10];
+  for (int i = 0; i < 10; ++i) {
+    coef[i] = (float)coeffs[i];
+    TORCH_CHECK(std::isfinite(coef[i]), "aiko.rgb_to_yuv_out: coefficient ", i, " is not finite in fp32");
+  }
+  TORCH_CHECK(rgb.scalar_type() == at::kByte && rgb.dim() == 4 && rgb.size(3) == 3 && rgb.is_contiguous() &&
+                  rgb.size(0) >= 1,
+              "aiko.rgb_to_yuv_out: rgb uint8 [B, H, W, 3] contiguous required");
+  const int64_t B = rgb.size(0), H = rgb.size(1), W = rgb.size(2);
+  TORCH_CHECK(H >= 1 && W >= 1 && H <= 32768 && W <= 32768,
+              "aiko.rgb_to_yuv_out: 1 <= height, width <= 32768 required, got ", H, " x ", W);
+  TORCH_CHECK(format != 3 || W % 2 == 0, "aiko.rgb_to_yuv_out: yuyv needs an even width, got ", W);
+  const int64_t cplane = ((H + 1) / 2) * ((W + 1) / 2);
+  const int64_t frame_bytes = format == 2 ? 3 * H * W : format == 3 ? 2 * H * W : H * W + 2 * cplane;
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.dim() == 2 && out.size(0) == B && out.is_contiguous(),
+              "aiko.rgb_to_yuv_out: out uint8 [B, frame_bytes] contiguous required");
+  TORCH_CHECK(out.size(1) == frame_bytes, "aiko.rgb_to_yuv_out: a ", H, " x ", W, " frame of this format has ",
+              frame_bytes, " bytes, out has ", out.size(1));
+  TORCH_CHECK(B <= 65535, "aiko.rgb_to_yuv_out: B = ", B, " exceeds the grid limit (65535 frames)");
+  const auto rp = reinterpret_cast<uintptr_t>(rgb.data_ptr()), op = reinterpret_cast<uintptr_t>(out.data_ptr());
+  TORCH_CHECK(rp + (uintptr_t)rgb.numel() <= op || op + (uintptr_t)out.numel() <= rp,
+              "aiko.rgb_to_yuv_out: rgb and out overlap");
+  check_launch(aiko_rgb_to_yuv_u8(rgb.data_ptr(), out.data_ptr(), B, H, W, (int)format, coef, (int)round_mode,
+                                  cur_stream()),
+               "rgb_to_yuv_u8");
+}
+
 void batchnorm_out(const at::Tensor& x, const at::Tensor& scale, const at::Tensor& shift, at::Tensor& y, int64_t act) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -1628,6 +1670,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("roi_crop_out(Tensor frames, Tensor det, Tensor count, int k, float margin, Tensor(a!) crops, Tensor(b!) rois) -> ()");
   m.def("draw_detections_out(Tensor frames, Tensor det, Tensor count, int k, Tensor? labels, Tensor? scores, Tensor names, Tensor font, Tensor palette, int glyph_width, int thickness, int text_scale, float margin, bool show_score, Tensor(a!) out) -> ()");
   m.def("yuv_to_rgb_out(Tensor raw, int height, int width, int format, float[] coeffs, int round_mode, Tensor(a!) out) -> ()");
+  m.def("rgb_to_yuv_out(Tensor rgb, int fmt, float[] coeffs, int round, Tensor(a!) out) -> ()");
   m.def("batchnorm_out(Tensor x, Tensor scale, Tensor shift, Tensor(a!) y, int act) -> ()");
   m.def("yolo_decode_out(Tensor[] feats, int[] strides, int nc, int reg_max, Tensor(a!) boxes, Tensor(b!) scores, Tensor(c!) cls) -> ()");
   m.def("topk_nms_out(Tensor boxes, Tensor scores, Tensor cls, int max_cand, float[] params, Tensor(a!) det, Tensor(b!) count) -> ()");
@@ -1678,6 +1721,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("roi_crop_out", &roi_crop_out);
   m.impl("draw_detections_out", &draw_detections_out);
   m.impl("yuv_to_rgb_out", &yuv_to_rgb_out);
+  m.impl("rgb_to_yuv_out", &rgb_to_yuv_out);
   m.impl("batchnorm_out", &batchnorm_out);
   m.impl("yolo_decode_out", &yolo_decode_out);
   m.impl("topk_nms_out", &topk_nms_out);

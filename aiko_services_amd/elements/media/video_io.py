@@ -92,18 +92,55 @@ def read_y4m(path) -> np.ndarray:
     return np.stack(list(iter_y4m(path)))
 
 
+def _rgb_to_yuv420(rgb):
+    """(y [H, W], u, v [ceil(H/2), ceil(W/2)]) of an RGB frame, 4:2:0 with centre ("jpeg") siting:
+    luma per pixel, each chroma sample from the mean RGB of its 2x2 block's in-frame pixels (2 or 1
+    at an odd right or bottom edge) — the integer sum of the bytes times 1/n, as
+    ``ops/yuv.py`` defines it for the device (``rgb_to_yuv``, ``i420``, ``jpeg``)."""
+    rgb = np.asarray(rgb)
+    h, w = rgb.shape[:2]
+    ph, pw = (h + 1) // 2 * 2, (w + 1) // 2 * 2
+    s = np.zeros((ph, pw, 3), np.int32)
+    s[:h, :w] = rgb
+    n = np.zeros((ph, pw), np.int32)
+    n[:h, :w] = 1
+    s = s.reshape(ph // 2, 2, pw // 2, 2, 3).sum((1, 3))
+    n = n.reshape(ph // 2, 2, pw // 2, 2).sum((1, 3))
+    mean = s.astype(np.float32) * (np.float32(1.0) / n.astype(np.float32))[..., None]
+    y = _rgb_to_yuv(rgb)[0]
+    _, u, v = _rgb_to_yuv(mean)
+    return y, u, v
+
+
 class Y4MWriter:
-    def __init__(self, path, width, height, fps=30):
+    """``chroma``: ``"444"`` (default) or ``"420jpeg"``, the file's ``C`` tag.  ``write`` converts an
+    RGB frame on the host; ``write_raw`` takes a frame's planes as they are: packed ``i444`` /
+    ``i420`` bytes (``ops.yuv``), for instance from ``RgbToYuv`` with the ``jpeg`` standard."""
+
+    def __init__(self, path, width, height, fps=30, chroma="444"):
+        if chroma not in ("444", "420jpeg"):
+            raise ValueError(f"Y4MWriter: chroma {chroma!r} not supported (444 or 420jpeg)")
         self.f = open(path, "wb")
-        self.w, self.h = width, height
-        self.f.write(f"YUV4MPEG2 W{width} H{height} F{int(fps)}:1 Ip A1:1 C444\n".encode())
+        self.w, self.h, self.chroma = int(width), int(height), chroma
+        cw, ch = (self.w, self.h) if chroma == "444" else ((self.w + 1) // 2, (self.h + 1) // 2)
+        self.frame_bytes = self.w * self.h + 2 * cw * ch
+        self.f.write(f"YUV4MPEG2 W{width} H{height} F{int(fps)}:1 Ip A1:1 C{chroma}\n".encode())
 
     def write(self, rgb):
-        y, u, v = _rgb_to_yuv(np.asarray(rgb)[: self.h, : self.w])
+        rgb = np.asarray(rgb)[: self.h, : self.w]
+        y, u, v = _rgb_to_yuv(rgb) if self.chroma == "444" else _rgb_to_yuv420(rgb)
         self.f.write(b"FRAME\n")
         self.f.write(y.tobytes())
         self.f.write(u.tobytes())
         self.f.write(v.tobytes())
+
+    def write_raw(self, packed):
+        packed = np.ascontiguousarray(np.asarray(packed, dtype=np.uint8)).reshape(-1)
+        if packed.size != self.frame_bytes:
+            raise ValueError(f"Y4MWriter: a C{self.chroma} frame of {self.w} x {self.h} has {self.frame_bytes} "
+                             f"bytes, got {packed.size}")
+        self.f.write(b"FRAME\n")
+        self.f.write(packed.tobytes())
 
     def close(self):
         self.f.close()
@@ -263,7 +300,25 @@ class VideoShow(PipelineElement):
 
 class VideoWriteFile(DataTarget):
     """Writes ``.avi`` (parameters ``codec``: ``MJPG`` (default) | ``raw``, ``quality``),
-    ``.gif``, ``.y4m`` or ``.npy``; other suffixes need OpenCV.  ``rate``: frames per second."""
+    ``.gif``, ``.y4m`` or ``.npy``; other suffixes need OpenCV.  ``rate``: frames per second.
+    ``raw: true`` (``.y4m`` only) with ``format: i420 | i444``, ``height`` and ``width``: 1-D
+    ``images`` are a frame's packed planes (``RgbToYuv`` then ``FrameDownload``) and are written
+    unconverted, ``C420jpeg`` or ``C444``; anything else is an error."""
+
+    _RAW_CHROMA = {"i420": "420jpeg", "i444": "444"}
+
+    def _raw_writer(self, path, suffix):
+        """``(Y4MWriter, None)`` for ``raw: true``, or ``(None, diagnostic)``."""
+        fmt = str(self.get_parameter("format", "")[0]).lower()
+        height, width = self.get_parameter("height", None)[0], self.get_parameter("width", None)[0]
+        if suffix != ".y4m":
+            return None, f"{path}: raw frames need a .y4m file"
+        if fmt not in self._RAW_CHROMA:
+            return None, f"{path}: raw format {fmt!r} cannot be written (i420 or i444)"
+        if height is None or width is None:
+            return None, f"{path}: raw frames need the height and width parameters"
+        rate, _ = self.get_parameter("rate", 30)
+        return Y4MWriter(path, int(width), int(height), float(rate), self._RAW_CHROMA[fmt]), None
 
     def __init__(self, context):
         context.set_protocol("video_write_file:0")
@@ -283,8 +338,20 @@ class VideoWriteFile(DataTarget):
     def process_frame(self, stream, images):
         path = stream.variables["video_path"]
         suffix = Path(path).suffix.lower()
+        raw = str(self.get_parameter("raw", False)[0]).lower() in ("true", "1", "yes")
+        if raw and stream.variables["video_writer"] is None:
+            writer, diagnostic = self._raw_writer(path, suffix)
+            if writer is None:
+                return StreamEvent.ERROR, {"diagnostic": diagnostic}
+            stream.variables["video_writer"] = writer
         for image in images:
             arr = np.asarray(image).astype(np.uint8)
+            if raw and arr.ndim == 1:
+                try:
+                    stream.variables["video_writer"].write_raw(arr)
+                except ValueError as exc:
+                    return StreamEvent.ERROR, {"diagnostic": str(exc)}
+                continue
             if suffix in (".npy", ".gif"):
                 stream.variables["video_frames"].append(arr)
                 continue

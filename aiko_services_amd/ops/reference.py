@@ -284,3 +284,56 @@ def yuv_to_rgb_ref(raw: torch.Tensor, height: int, width: int, fmt: str, standar
     else:
         rgb = (rgb + 0.5).clamp_(0, 255)                    # the cast truncates
     return rgb.to(torch.uint8)
+
+
+# ---- YUV egress -----------------------------------------------------------------------------
+
+def _chroma_mean_ref(rgb: torch.Tensor, by: int, bx: int) -> torch.Tensor:
+    """fp32 ``[B, ceil(H/by), ceil(W/bx), 3]``: the mean RGB of each ``by`` x ``bx`` block's
+    in-frame pixels (``by``, ``bx`` in {1, 2}): the integer sum of the bytes times 1/n."""
+    B, H, W, _ = rgb.shape
+    ph, pw = -(-H // by) * by, -(-W // bx) * bx
+    s = torch.zeros(B, ph, pw, 3, dtype=torch.int32)
+    s[:, :H, :W] = rgb.to(torch.int32)
+    n = torch.zeros(ph, pw, dtype=torch.int32)
+    n[:H, :W] = 1
+    s = s.view(B, ph // by, by, pw // bx, bx, 3).sum((2, 4))
+    n = n.view(ph // by, by, pw // bx, bx).sum((1, 3))
+    inv = (1.0 / n.to(torch.float32))[None, :, :, None]                 # 1, 0.5 or 0.25: exact
+    return s.to(torch.float32) * inv
+
+
+def rgb_to_yuv_ref(rgb: torch.Tensor, fmt: str, standard: str) -> torch.Tensor:
+    """``ops.yuv.rgb_to_yuv`` with torch fp32 on the CPU, the formula of :mod:`~aiko_services_amd.ops.yuv`
+    literally: one rounding per operation, the constants as fp32 tensors from the same
+    ``ENCODE_STANDARDS`` row the kernel is given.  uint8 ``[B, H, W, 3]`` -> uint8 ``[B, frame_bytes]``."""
+    from .yuv import ENCODE_STANDARDS, FORMATS, frame_bytes
+    if fmt not in FORMATS:
+        raise ValueError(f"rgb_to_yuv_ref: unknown format {fmt!r}")
+    coeffs, rounding = ENCODE_STANDARDS[standard]
+    yoff, yr, yg, yb, ur, ug, ub, vr, vg, vb = (torch.tensor(c, dtype=torch.float32) for c in coeffs)
+    rgb = rgb.cpu()
+    if rgb.dim() != 4 or rgb.dtype != torch.uint8 or rgb.shape[3] != 3:
+        raise ValueError(f"rgb_to_yuv_ref: uint8 [B, H, W, 3] required, got {tuple(rgb.shape)}")
+    B, H, W, _ = rgb.shape
+    nbytes = frame_bytes(fmt, H, W)                                     # yuyv with an odd width: ValueError
+
+    def level(x):
+        if rounding == "rint":
+            return torch.round(x).clamp_(0, 255).to(torch.uint8)        # ties to even
+        return (x + 0.5).clamp_(0, 255).to(torch.uint8)                 # the cast truncates
+
+    f = rgb.to(torch.float32)
+    y = level(((yr * f[..., 0] + yg * f[..., 1]) + yb * f[..., 2]) + yoff)
+    by, bx = {"nv12": (2, 2), "i420": (2, 2), "yuyv": (1, 2), "i444": (1, 1)}[fmt]
+    m = f if fmt == "i444" else _chroma_mean_ref(rgb, by, bx)
+    u = level(((ur * m[..., 0] + ug * m[..., 1]) + ub * m[..., 2]) + 128.0)
+    v = level(((vr * m[..., 0] + vg * m[..., 1]) + vb * m[..., 2]) + 128.0)
+    if fmt == "yuyv":
+        out = torch.stack([y[..., 0::2], u, y[..., 1::2], v], -1).reshape(B, -1)
+    elif fmt == "nv12":
+        out = torch.cat([y.reshape(B, -1), torch.stack([u, v], -1).reshape(B, -1)], 1)
+    else:
+        out = torch.cat([y.reshape(B, -1), u.reshape(B, -1), v.reshape(B, -1)], 1)
+    assert out.shape[1] == nbytes
+    return out.contiguous()
