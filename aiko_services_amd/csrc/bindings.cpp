@@ -79,6 +79,8 @@ int aiko_yuv_to_rgb_u8(const void* raw, void* out, int B, int H, int W, int fmt,
                        hipStream_t stream);
 int aiko_rgb_to_yuv_u8(const void* rgb, void* out, int B, int H, int W, int fmt, const float* coef, int half,
                        hipStream_t stream);
+int aiko_resample(const void* pcm, int is_f32, const float* hist, const float* filt, float* out, float* hist_out,
+                  int B, long n_in, int C, int L, int M, int T, hipStream_t stream);
 int aiko_batchnorm(const void* x, void* y, const float* scale, const float* shift, long P, int C, int ldx,
                    int ldy, int act, hipStream_t stream);
 int aiko_upsample2x(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy,
@@ -1224,6 +1226,70 @@ void window_shift_out(const at::Tensor& src, const at::Tensor& chunk, at::Tensor
                                  cur_stream()), "window_shift");
 }
 
+// out [B, n_in L / M], hist_out [B, T-1] <- pcm [B, n_in, C] (int16 or fp32, interleaved), the
+// stream's previous T-1 mono samples hist [B, T-1] and the polyphase taps filt [L, T]
+// (resample_ops.hip; the arithmetic is in ops/audio.py)
+void resample_out(const at::Tensor& pcm, const at::Tensor& hist, const at::Tensor& filt, int64_t L, int64_t M,
+                  at::Tensor& out, at::Tensor& hist_out) {
+  check_cuda(pcm, "pcm");
+  check_cuda(hist, "hist");
+  check_cuda(filt, "filt");
+  check_cuda(out, "out");
+  check_cuda(hist_out, "hist_out");
+  TORCH_CHECK(pcm.device() == hist.device() && pcm.device() == filt.device() && pcm.device() == out.device() &&
+                  pcm.device() == hist_out.device(),
+              "aiko.resample_out: tensors on different devices");
+  TORCH_CHECK((pcm.scalar_type() == at::kShort || pcm.scalar_type() == at::kFloat) && pcm.dim() == 3 &&
+                  pcm.is_contiguous() && pcm.size(0) >= 1 && pcm.size(1) >= 1,
+              "aiko.resample_out: pcm int16 or fp32 [B, n_in, C] contiguous required");
+  const int64_t B = pcm.size(0), n_in = pcm.size(1), C = pcm.size(2);
+  TORCH_CHECK(C >= 1 && C <= 8, "aiko.resample_out: 1 <= C <= 8 channels required, got ", C);
+  TORCH_CHECK(L >= 1 && M >= 1 && L <= 16384 && M <= (1 << 24), "aiko.resample_out: bad ratio L / M = ", L, " / ", M);
+  TORCH_CHECK(filt.scalar_type() == at::kFloat && filt.dim() == 2 && filt.size(0) == L && filt.size(1) >= 1 &&
+                  filt.is_contiguous(),
+              "aiko.resample_out: filt fp32 [L, T] contiguous required, L = ", L);
+  const int64_t T = filt.size(1);
+  TORCH_CHECK(L * T <= 16384, "aiko.resample_out: L * T = ", L * T, " taps exceed 16384 (64 KiB)");
+  const int64_t span = (1023 * M + L - 1) / L + T;     // samples a tile of 1024 outputs reads
+  TORCH_CHECK(4 * (L * T + span) <= 160 * 1024, "aiko.resample_out: taps and a tile's ", span,
+              " samples exceed 160 KiB of LDS (M / L too large)");
+  TORCH_CHECK(n_in <= (1 << 30) && n_in * C <= (1 << 30), "aiko.resample_out: n_in * C = ", n_in * C,
+              " exceeds 2^30");
+  TORCH_CHECK(n_in * L % M == 0, "aiko.resample_out: n_in * L % M != 0 (n_in = ", n_in, ", L / M = ", L, " / ", M,
+              "): a chunk must end at phase 0");
+  const int64_t n_out = n_in * L / M;
+  TORCH_CHECK(n_out <= (1 << 30), "aiko.resample_out: n_out = ", n_out, " exceeds 2^30");
+  TORCH_CHECK(hist.scalar_type() == at::kFloat && hist.dim() == 2 && hist.size(0) == B && hist.size(1) == T - 1 &&
+                  hist.is_contiguous(),
+              "aiko.resample_out: hist fp32 [B, T-1] = [", B, ", ", T - 1, "] contiguous required");
+  TORCH_CHECK(hist_out.scalar_type() == at::kFloat && hist_out.dim() == 2 && hist_out.size(0) == B &&
+                  hist_out.size(1) == T - 1 && hist_out.is_contiguous(),
+              "aiko.resample_out: hist_out fp32 [B, T-1] = [", B, ", ", T - 1, "] contiguous required");
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.dim() == 2 && out.size(0) == B && out.size(1) == n_out &&
+                  out.is_contiguous(),
+              "aiko.resample_out: out fp32 [B, n_out] = [", B, ", ", n_out, "] contiguous required");
+  TORCH_CHECK(B <= 65535, "aiko.resample_out: B = ", B, " exceeds the grid limit (65535 streams)");
+  // neither output may overlap an input or the other output
+  const at::Tensor* ins[3] = {&pcm, &hist, &filt};
+  const char* in_names[3] = {"pcm", "hist", "filt"};
+  const at::Tensor* outs[2] = {&out, &hist_out};
+  const char* out_names[2] = {"out", "hist_out"};
+  auto overlap = [](const at::Tensor& x, const at::Tensor& y) {
+    const auto xp = reinterpret_cast<uintptr_t>(x.data_ptr()), yp = reinterpret_cast<uintptr_t>(y.data_ptr());
+    const uintptr_t xn = x.numel() * x.element_size(), yn = y.numel() * y.element_size();
+    return xn > 0 && yn > 0 && xp < yp + yn && yp < xp + xn;
+  };
+  for (int o = 0; o < 2; ++o) {
+    for (int i = 0; i < 3; ++i)
+      TORCH_CHECK(!overlap(*outs[o], *ins[i]), "aiko.resample_out: ", out_names[o], " and ", in_names[i], " overlap");
+  }
+  TORCH_CHECK(!overlap(out, hist_out), "aiko.resample_out: out and hist_out overlap");
+  check_launch(aiko_resample(pcm.data_ptr(), pcm.scalar_type() == at::kFloat ? 1 : 0, hist.data_ptr<float>(),
+                             filt.data_ptr<float>(), out.data_ptr<float>(), hist_out.data_ptr<float>(), (int)B,
+                             (long)n_in, (int)C, (int)L, (int)M, (int)T, cur_stream()),
+               "resample");
+}
+
 void avgpool_out(const at::Tensor& x, at::Tensor& y) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -1685,6 +1751,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("avgpool_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("mean_rows_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("window_shift_out(Tensor src, Tensor chunk, Tensor(a!) dst) -> ()");
+  m.def("resample_out(Tensor pcm, Tensor hist, Tensor filt, int L, int M, Tensor(a!) out, Tensor(b!) hist_out) -> ()");
   m.def("zero_border_rows_(Tensor(a!) x, int rows) -> ()");
   m.def("sppf_pool_(Tensor(a!) cat, int c, int k) -> ()");
   m.def("stem_pool_out(Tensor x, Tensor w, Tensor bias, Tensor(a!) y, int Ho, int Wo, int variant=0) -> ()");
@@ -1728,6 +1795,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("avgpool_out", &avgpool_out);
   m.impl("mean_rows_out", &mean_rows_out);
   m.impl("window_shift_out", &window_shift_out);
+  m.impl("resample_out", &resample_out);
   m.impl("zero_border_rows_", &zero_border_rows_);
   m.impl("sppf_pool_", &sppf_pool_);
   m.impl("stem_pool_out", &stem_pool_out);

@@ -1,3 +1,5 @@
-"""GPU-resident elements (MI355X): synthetic decode, raw YUV ingest and egress, preprocess, ResNet-50, top-k."""
+"""GPU-resident elements (MI355X): synthetic decode, raw YUV ingest and egress, raw PCM ingest, preprocess,
+ResNet-50, top-k."""
+from .audio_ingest import AudioResample  # noqa: F401
 from .egress import FrameDownload, RgbToYuv  # noqa: F401
 from .ingest import YuvToRgb  # noqa: F401

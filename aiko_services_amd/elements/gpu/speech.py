@@ -5,7 +5,9 @@
 * ``AudioChunks``   — ``streams`` concurrent audio streams, each producing a ``chunk``-second
   16 kHz chunk per frame directly in HBM (synthetic: tones + noise from a rotating pool), or
   uploads host chunks (numpy / CPU tensors from ``AudioReadFile`` / ``AudioSynthetic``) through
-  pinned staging buffers;
+  pinned staging buffers; ``format: pcm16`` (default ``f32``) keeps the samples as a sound card or
+  a WAV file delivers them — interleaved int16, ``channels`` per frame at ``sample_rate`` — host
+  chunks uploaded unconverted, for ``AudioResample`` (``elements/gpu/audio_ingest.py``);
 * ``AudioWindow``   — per-stream sliding window of the last ``window`` seconds kept on the GPU
   (the reference's ``PE_AudioFraming`` LRU of chunks, ``examples/speech/speech_elements.py:
   60-83``, as one device ring per stream: shift + append, no host copies);
@@ -46,6 +48,42 @@ class AudioChunks(GpuPipelineElement):
         self._cursor = 0
         self._pinned: list = []
         self._pin_slot = 0
+        self._raw = self._pcm16()
+
+    def _pcm16(self) -> bool:
+        fmt = str(_p(self, "format", "f32")).lower()
+        if fmt not in ("f32", "pcm16"):
+            raise ValueError(f"AudioChunks: unknown format {fmt!r} (f32 or pcm16)")
+        return fmt == "pcm16"
+
+    def _synthetic_pcm16(self):
+        """The synthetic pool as a sound card delivers it: interleaved int16 ``[B, n, channels]`` at
+        ``sample_rate``, each channel its own tone (for ``AudioResample``)."""
+        if self._pool is None:
+            B, C = int(_p(self, "streams", 8)), int(_p(self, "channels", 1))
+            rate = int(_p(self, "sample_rate", RATE))
+            n = int(float(_p(self, "chunk", 5.0)) * rate)
+            g = torch.Generator(device=self.device).manual_seed(int(_p(self, "seed", 0)))
+            t = torch.arange(n, device=self.device, dtype=torch.float32)[None, :, None] / rate
+            self._pool = []
+            for _ in range(int(_p(self, "pool", 4))):
+                f = 100 + 900 * torch.rand(B, 1, C, device=self.device, generator=g)
+                noise = 0.02 * torch.randn(B, n, C, device=self.device, generator=g)
+                x = 0.3 * torch.sin(2 * torch.pi * f * t) + noise
+                self._pool.append(torch.round(x * 32767.0).clamp(-32768, 32767).to(torch.int16).contiguous())
+        x = self._pool[self._cursor % len(self._pool)]
+        self._cursor += 1
+        return x
+
+    def _upload_pcm16(self, audio):
+        """Host int16 PCM as it arrives, unconverted: ``[n]`` or ``[n, channels]`` of one stream,
+        ``[B, n*channels]`` or ``[B, n, channels]`` -> the same samples on the device, ``B`` first."""
+        x = audio if isinstance(audio, torch.Tensor) else torch.as_tensor(np.asarray(audio))
+        if x.dtype != torch.int16:
+            raise ValueError(f"AudioChunks: format pcm16 takes int16 samples, got {x.dtype}")
+        if x.dim() == 1 or (x.dim() == 2 and x.shape[1] == int(_p(self, "channels", 1))):
+            x = x[None]
+        return x if x.device.type == "cuda" else self._pinned_upload(x, torch.int16)
 
     def _synthetic(self):
         if self._pool is None:
@@ -68,8 +106,11 @@ class AudioChunks(GpuPipelineElement):
             x = x[None]
         if x.device.type == "cuda":
             return x.float()
-        if not self._pinned or self._pinned[0][0].shape != x.shape:
-            self._pinned = [[torch.empty(x.shape, dtype=torch.float32, pin_memory=True), None]
+        return self._pinned_upload(x, torch.float32)
+
+    def _pinned_upload(self, x, dtype):
+        if not self._pinned or self._pinned[0][0].shape != x.shape or self._pinned[0][0].dtype != dtype:
+            self._pinned = [[torch.empty(x.shape, dtype=dtype, pin_memory=True), None]
                             for _ in range(4)]
         slot = self._pinned[self._pin_slot]
         self._pin_slot = (self._pin_slot + 1) % len(self._pinned)
@@ -82,7 +123,10 @@ class AudioChunks(GpuPipelineElement):
         return out
 
     def process_frame(self, stream, audio_samples=None, **kwargs):
-        audio = self._synthetic() if audio_samples is None else self._upload(audio_samples)
+        if self._raw:
+            audio = self._synthetic_pcm16() if audio_samples is None else self._upload_pcm16(audio_samples)
+        else:
+            audio = self._synthetic() if audio_samples is None else self._upload(audio_samples)
         return StreamEvent.OKAY, {"audio": audio, "t_submit": time.perf_counter()}
 
 

@@ -32,7 +32,7 @@ __all__ = ["AudioOutput", "AudioReadFile", "AudioWriteFile", "AudioFraming", "Au
            "PE_FFT", "AudioSynthetic", "PE_AudioFilter", "PE_AudioResampler", "PE_GraphXY",
            "PE_MicrophonePA", "PE_MicrophoneSD", "PE_Speaker", "PE_RemoteSend0", "PE_RemoteSend1",
            "PE_RemoteSend2", "PE_RemoteReceive0", "PE_RemoteReceive1", "PE_RemoteReceive2",
-           "encode_array", "decode_array", "read_wav", "write_wav"]
+           "encode_array", "decode_array", "read_wav", "read_wav_raw", "write_wav"]
 
 
 def read_wav(path):
@@ -76,8 +76,22 @@ class AudioOutput(PipelineElement):
         return StreamEvent.OKAY, {"audio_samples": audio_samples}
 
 
+def read_wav_raw(path):
+    """16-bit PCM WAV -> (int16 ``[n, C]`` as stored, rate): no normalisation, no downmix."""
+    with wave.open(str(path), "rb") as w:
+        rate, ch, width, n = w.getframerate(), w.getnchannels(), w.getsampwidth(), w.getnframes()
+        raw = w.readframes(n)
+    if width != 2:
+        raise ValueError(f"{8 * width}-bit samples (raw reads take 16-bit PCM)")
+    return np.frombuffer(raw, np.int16).reshape(-1, ch), rate
+
+
 class AudioReadFile(DataSource):
-    """WAV files -> chunks of ``chunk_duration`` s (default 5 s) at ``sample_rate`` (16 kHz)."""
+    """WAV files -> chunks of ``chunk_duration`` s (default 5 s) at ``sample_rate`` (16 kHz):
+    float32 mono, resampled on the host.  ``raw: true`` hands the file's 16-bit PCM out as it is
+    stored instead — int16 ``[n, C]`` chunks at the file's own rate, which must equal
+    ``sample_rate``, the last one zero-padded — for conversion on the device
+    (``AudioChunks`` with ``format: pcm16``, then ``AudioResample``)."""
 
     def __init__(self, context):
         context.set_protocol("audio_read_file:0")
@@ -99,6 +113,17 @@ class AudioReadFile(DataSource):
                 c = np.pad(c, (0, n - len(c)))
             yield c
 
+    def _chunks_raw(self, path):
+        """The file is read and checked here, not at the first chunk: a wrong rate or sample width
+        is the caller's ``ERROR``."""
+        rate_out, _ = self.get_parameter("sample_rate", 16000)
+        dur, _ = self.get_parameter("chunk_duration", 5.0)
+        x, rate = read_wav_raw(path)
+        if rate != int(rate_out):
+            raise ValueError(f"sample rate {rate} Hz, sample_rate parameter {int(rate_out)} Hz")
+        n = int(float(dur) * int(rate_out))
+        return (np.pad(x[i:i + n], ((0, n - len(x[i:i + n])), (0, 0))) for i in range(0, len(x), n))
+
     def frame_generator(self, stream, frame_id):
         gen = stream.variables.get("audio_chunks")
         while True:
@@ -107,9 +132,10 @@ class AudioReadFile(DataSource):
                     path, _ = next(stream.variables["source_paths_generator"])
                 except StopIteration:
                     return StreamEvent.STOP, {"diagnostic": "End of audio file(s)"}
+                raw, _ = self.get_parameter("raw", False)
                 try:
-                    gen = self._chunks(path)
-                except (wave.Error, EOFError, KeyError) as exc:
+                    gen = self._chunks_raw(path) if str(raw).lower() in ("true", "1", "yes") else self._chunks(path)
+                except (wave.Error, EOFError, KeyError, ValueError) as exc:
                     return StreamEvent.ERROR, {"diagnostic": f"Couldn't open audio file {path}: {exc}"}
                 stream.variables["audio_chunks"] = gen
             try:
