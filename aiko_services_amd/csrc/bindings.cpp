@@ -81,6 +81,10 @@ int aiko_rgb_to_yuv_u8(const void* rgb, void* out, int B, int H, int W, int fmt,
                        hipStream_t stream);
 int aiko_resample(const void* pcm, int is_f32, const float* hist, const float* filt, float* out, float* hist_out,
                   int B, long n_in, int C, int L, int M, int T, hipStream_t stream);
+int aiko_track_detections(const float* det, const int* count, const float* boxes, const int* meta, const int* issued,
+                          float* boxes_out, int* meta_out, int* issued_out, int* ids, int* hits, int* labels, int B,
+                          int max_det, int K, int T, float thr, int max_age, float min_score, int class_aware,
+                          int label_mod, hipStream_t stream);
 int aiko_batchnorm(const void* x, void* y, const float* scale, const float* shift, long P, int C, int ldx,
                    int ldy, int act, hipStream_t stream);
 int aiko_upsample2x(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy,
@@ -1290,6 +1294,81 @@ void resample_out(const at::Tensor& pcm, const at::Tensor& hist, const at::Tenso
                "resample");
 }
 
+// One tracker step (track_ops.hip; the rules are in ops/track.py): det [B, max_det, 6] / count [B] and
+// the state boxes [B, T, 4] / meta [B, T, 4] / issued [B] -> the next state in boxes_out / meta_out /
+// issued_out and, per ROI slot b*k + i, the track's id, its hits and the overlay's label
+void track_detections_out(const at::Tensor& det, const at::Tensor& count, const at::Tensor& boxes,
+                          const at::Tensor& meta, const at::Tensor& issued, int64_t k, double iou, int64_t max_age,
+                          double min_score, bool class_aware, int64_t label_mod, at::Tensor& boxes_out,
+                          at::Tensor& meta_out, at::Tensor& issued_out, at::Tensor& ids, at::Tensor& hits,
+                          at::Tensor& labels) {
+  const at::Tensor* ins[5] = {&det, &count, &boxes, &meta, &issued};
+  const char* in_names[5] = {"det", "count", "boxes", "meta", "issued"};
+  const at::Tensor* outs[6] = {&boxes_out, &meta_out, &issued_out, &ids, &hits, &labels};
+  const char* out_names[6] = {"boxes_out", "meta_out", "issued_out", "ids", "hits", "labels"};
+  for (int i = 0; i < 5; ++i) check_cuda(*ins[i], in_names[i]);
+  for (int o = 0; o < 6; ++o) check_cuda(*outs[o], out_names[o]);
+  for (int i = 1; i < 5; ++i)
+    TORCH_CHECK(ins[i]->device() == det.device(), "aiko.track_detections_out: tensors on different devices");
+  for (int o = 0; o < 6; ++o)
+    TORCH_CHECK(outs[o]->device() == det.device(), "aiko.track_detections_out: tensors on different devices");
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(2) == 6 && det.is_contiguous() &&
+                  det.size(0) >= 1,
+              "aiko.track_detections_out: det fp32 [B, max_det, 6] contiguous required");
+  const int64_t B = det.size(0), max_det = det.size(1);
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 && count.size(0) == B && count.is_contiguous(),
+              "aiko.track_detections_out: count int32 [B] contiguous required");
+  TORCH_CHECK(k >= 1 && k <= 64, "aiko.track_detections_out: 1 <= k <= 64 required, got ", k);
+  TORCH_CHECK(k <= max_det, "aiko.track_detections_out: k <= max_det (", max_det, ") required, got ", k);
+  TORCH_CHECK(boxes.scalar_type() == at::kFloat && boxes.dim() == 3 && boxes.size(2) == 4 && boxes.is_contiguous(),
+              "aiko.track_detections_out: boxes fp32 [B, T, 4] contiguous required");
+  const int64_t T = boxes.size(1);
+  TORCH_CHECK(T >= 1 && T <= 64, "aiko.track_detections_out: 1 <= T <= 64 track slots required, got ", T);
+  TORCH_CHECK(boxes.size(0) == B, "aiko.track_detections_out: state of ", boxes.size(0), " rows for B = ", B);
+  auto is_state = [&](const at::Tensor& bx, const at::Tensor& mt, const at::Tensor& is) {
+    return bx.scalar_type() == at::kFloat && bx.dim() == 3 && bx.size(0) == B && bx.size(1) == T &&
+           bx.size(2) == 4 && bx.is_contiguous() && mt.scalar_type() == at::kInt && mt.dim() == 3 &&
+           mt.size(0) == B && mt.size(1) == T && mt.size(2) == 4 && mt.is_contiguous() &&
+           is.scalar_type() == at::kInt && is.dim() == 1 && is.size(0) == B && is.is_contiguous();
+  };
+  TORCH_CHECK(is_state(boxes, meta, issued), "aiko.track_detections_out: state boxes fp32 [B, T, 4], meta int32 "
+              "[B, T, 4], issued int32 [B] contiguous required, B = ", B, ", T = ", T);
+  TORCH_CHECK(is_state(boxes_out, meta_out, issued_out), "aiko.track_detections_out: state_out boxes fp32 [B, T, 4], "
+              "meta int32 [B, T, 4], issued int32 [B] contiguous required, B = ", B, ", T = ", T);
+  TORCH_CHECK(B <= 65535, "aiko.track_detections_out: B = ", B, " exceeds the grid limit (65535 rows)");
+  for (const at::Tensor* t : {&ids, &hits, &labels})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1 && t->size(0) == B * k && t->is_contiguous(),
+                "aiko.track_detections_out: ids, hits and labels int32 [B*k] = [", B * k, "] contiguous required");
+  TORCH_CHECK((float)iou > 0.f && (float)iou <= 1.f, "aiko.track_detections_out: 0 < iou <= 1 required, got ", iou);
+  TORCH_CHECK(max_age >= 0 && max_age <= INT_MAX, "aiko.track_detections_out: max_age >= 0 required, got ", max_age);
+  TORCH_CHECK(label_mod >= 1 && label_mod <= INT_MAX, "aiko.track_detections_out: label_mod >= 1 required, got ",
+              label_mod);
+  for (const at::Tensor* t : {&boxes, &meta, outs[0], outs[1]})
+    TORCH_CHECK(reinterpret_cast<uintptr_t>(t->data_ptr()) % 16 == 0,
+                "aiko.track_detections_out: boxes and meta 16-byte aligned");
+  // no output may overlap an input or another output
+  auto overlap = [](const at::Tensor& x, const at::Tensor& y) {
+    const auto xp = reinterpret_cast<uintptr_t>(x.data_ptr()), yp = reinterpret_cast<uintptr_t>(y.data_ptr());
+    const uintptr_t xn = x.numel() * x.element_size(), yn = y.numel() * y.element_size();
+    return xn > 0 && yn > 0 && xp < yp + yn && yp < xp + xn;
+  };
+  for (int o = 0; o < 6; ++o) {
+    for (int i = 0; i < 5; ++i)
+      TORCH_CHECK(!overlap(*outs[o], *ins[i]), "aiko.track_detections_out: ", out_names[o], " and ", in_names[i],
+                  " overlap");
+    for (int p = 0; p < o; ++p)
+      TORCH_CHECK(!overlap(*outs[o], *outs[p]), "aiko.track_detections_out: ", out_names[o], " and ", out_names[p],
+                  " overlap");
+  }
+  check_launch(aiko_track_detections(det.data_ptr<float>(), count.data_ptr<int>(), boxes.data_ptr<float>(),
+                                     meta.data_ptr<int>(), issued.data_ptr<int>(), boxes_out.data_ptr<float>(),
+                                     meta_out.data_ptr<int>(), issued_out.data_ptr<int>(), ids.data_ptr<int>(),
+                                     hits.data_ptr<int>(), labels.data_ptr<int>(), (int)B, (int)max_det, (int)k, (int)T,
+                                     (float)iou, (int)max_age, (float)min_score, class_aware ? 1 : 0, (int)label_mod,
+                                     cur_stream()),
+               "track_detections");
+}
+
 void avgpool_out(const at::Tensor& x, at::Tensor& y) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -1751,6 +1830,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("avgpool_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("mean_rows_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("window_shift_out(Tensor src, Tensor chunk, Tensor(a!) dst) -> ()");
+  m.def("track_detections_out(Tensor det, Tensor count, Tensor boxes, Tensor meta, Tensor issued, int k, float iou, int max_age, float min_score, bool class_aware, int label_mod, Tensor(a!) boxes_out, Tensor(b!) meta_out, Tensor(c!) issued_out, Tensor(d!) ids, Tensor(e!) hits, Tensor(f!) labels) -> ()");
   m.def("resample_out(Tensor pcm, Tensor hist, Tensor filt, int L, int M, Tensor(a!) out, Tensor(b!) hist_out) -> ()");
   m.def("zero_border_rows_(Tensor(a!) x, int rows) -> ()");
   m.def("sppf_pool_(Tensor(a!) cat, int c, int k) -> ()");
@@ -1796,6 +1876,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("mean_rows_out", &mean_rows_out);
   m.impl("window_shift_out", &window_shift_out);
   m.impl("resample_out", &resample_out);
+  m.impl("track_detections_out", &track_detections_out);
   m.impl("zero_border_rows_", &zero_border_rows_);
   m.impl("sppf_pool_", &sppf_pool_);
   m.impl("stem_pool_out", &stem_pool_out);

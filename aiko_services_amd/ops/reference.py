@@ -373,3 +373,106 @@ def resample_ref(pcm: torch.Tensor, hist: torch.Tensor, filt: torch.Tensor, L: i
         prod = filt[p, k][None, :] * s[:, i0 + k]
         acc = acc + prod
     return acc, s[:, n_in:n_in + T - 1].clone()
+
+
+# ---- tracker --------------------------------------------------------------------------------
+
+def _wrap_i32(v: int) -> int:
+    return (int(v) + 2 ** 31) % 2 ** 32 - 2 ** 31
+
+
+def track_ref(det: torch.Tensor, count: torch.Tensor, state, k: int, *, iou: float = 0.3, max_age: int = 30,
+              min_score: float = 0.0, class_aware: bool = True, label_mod: int = 1000):
+    """The definition of :func:`aiko_services_amd.ops.track.track_detections` on the CPU, in plain
+    loops: ``(ids, hits, labels, state_out)`` for ``det`` ``[B, max_det, 6]``, ``count`` ``[B]`` and a
+    ``TrackState``.  The pair geometry is numpy fp32, one rounding per operation; the threshold
+    test and the order of two pairs are products of those fp32 values as Python floats (doubles),
+    which are exact.  The integer fields wrap like int32.  ``state`` is not modified."""
+    import functools
+
+    import numpy as np
+
+    from .track import TrackState
+    det = det.detach().cpu().to(torch.float32).numpy()
+    count = count.detach().cpu().numpy()
+    boxes = state.boxes.detach().cpu().to(torch.float32).numpy().copy()
+    meta = state.meta.detach().cpu().numpy().astype(np.int64)
+    issued = state.issued.detach().cpu().numpy().astype(np.int64)
+    B, T = boxes.shape[:2]
+    k = int(k)
+    thr, floor = float(np.float32(iou)), np.float32(min_score)
+    ids = np.zeros((B, k), np.int64)
+    hits = np.zeros((B, k), np.int64)
+    labels = np.full((B, k), -1, np.int64)
+
+    def before(p, q):                                   # order of two pairs (t, d, inter, union)
+        lhs, rhs = p[2] * q[3], q[2] * p[3]
+        if lhs != rhs:
+            return -1 if lhs > rhs else 1
+        return -1 if p[:2] < q[:2] else 1
+
+    for b in range(B):
+        n = min(max(int(count[b]), 0), k)
+        rows = det[b, :n]                               # rows at or past count[b] are never read
+        valid = [i for i in range(n) if np.isfinite(rows[i, :4]).all()]
+        cls = [0 if c != c else int(min(max(float(c), -2.0 ** 31), 2.0 ** 31 - 1)) for c in rows[:, 5]]
+        live = [t for t in range(T) if meta[b, t, 0] != 0]
+        with np.errstate(all="ignore"):                 # a garbage state may hold inf and NaN
+            a, d = boxes[b][:, None, :], rows[None, :, :4]
+            aw, ah = a[..., 2] - a[..., 0], a[..., 3] - a[..., 1]
+            area_a = aw * ah
+            bw, bh = d[..., 2] - d[..., 0], d[..., 3] - d[..., 1]
+            area_b = bw * bh
+            zero = np.float32(0)
+            iw = np.maximum(np.minimum(a[..., 2], d[..., 2]) - np.maximum(a[..., 0], d[..., 0]), zero)
+            ih = np.maximum(np.minimum(a[..., 3], d[..., 3]) - np.maximum(a[..., 1], d[..., 1]), zero)
+            inter = iw * ih
+            union = (area_a + area_b) - inter
+        assert inter.dtype == np.float32 and union.dtype == np.float32
+        pairs = []
+        for t in live:
+            for i in valid:
+                if class_aware and cls[i] != meta[b, t, 1]:
+                    continue
+                it, un = float(inter[t, i]), float(union[t, i])
+                if it > 0 and un > 0 and it >= thr * un:
+                    pairs.append((t, i, it, un))
+        pairs.sort(key=functools.cmp_to_key(before))
+        of_track, of_det = {}, {}
+        for t, i, _, _ in pairs:
+            if t not in of_track and i not in of_det:
+                of_track[t], of_det[i] = i, t
+        for t in live:
+            if t in of_track:
+                i = of_track[t]
+                boxes[b, t] = rows[i, :4]
+                if not class_aware:
+                    meta[b, t, 1] = cls[i]
+                meta[b, t, 2] = _wrap_i32(meta[b, t, 2] + 1)
+                meta[b, t, 3] = 0
+            else:
+                meta[b, t, 3] = _wrap_i32(meta[b, t, 3] + 1)
+                if meta[b, t, 3] > int(max_age):
+                    meta[b, t] = 0
+        for t in range(T):                              # a free slot is all zeros
+            if meta[b, t, 0] == 0:
+                meta[b, t] = 0
+                boxes[b, t] = 0
+        for i in valid:
+            if i in of_det or not rows[i, 4] >= floor:
+                continue
+            free = [t for t in range(T) if meta[b, t, 0] == 0]
+            if not free:
+                break
+            t = free[0]
+            issued[b] = _wrap_i32(issued[b] + 1)
+            boxes[b, t] = rows[i, :4]
+            meta[b, t] = (issued[b], cls[i], 1, 0)
+            of_det[i] = t
+        for i, t in of_det.items():
+            ids[b, i], hits[b, i] = meta[b, t, 0], meta[b, t, 2]
+            if ids[b, i] > 0:
+                labels[b, i] = ids[b, i] % int(label_mod)
+    out = [torch.from_numpy(x.astype(np.int32)).reshape(-1) for x in (ids, hits, labels)]
+    return (*out, TrackState(torch.from_numpy(boxes), torch.from_numpy(meta.astype(np.int32)),
+                             torch.from_numpy(issued.astype(np.int32))))
