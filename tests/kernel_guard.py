@@ -7,7 +7,9 @@ from :func:`guarded` sits between two guards the test owns:
 
 * both guards (and, for an output, the interior) hold NaN — bf16 ``0x7FC0``, the fp32 quiet NaN,
   ``0xA5`` bytes for integer types — so an out-of-tensor read that reaches an accumulator makes
-  the output non-finite;
+  the output non-finite.  ``0xA5`` is a finite number when a 1-byte tensor stores fp8 values or
+  E8M0 block scales: ``guarded(..., poison=0xFF)`` fills such a tensor with ``0xFF`` instead, which
+  is NaN both as e4m3fn and as an E8M0 scale;
 * ``check()`` compares both guards bit for bit against a saved copy, so an out-of-tensor store
   is reported with its side and first offset.
 
@@ -49,11 +51,14 @@ class GuardError(AssertionError):
         super().__init__(f"guard {side} {name or 'tensor'} changed: first difference {where}")
 
 
+BYTE_NAN = 0xFF        # NaN as e4m3fn (S.1111.111) and as an E8M0 scale: the poison of fp8 storage
+
+
 def _poison_(flat: torch.Tensor, poison=None) -> None:
     if flat.dtype.is_floating_point:
         flat.fill_(float("nan") if poison is None else poison)
     else:
-        flat.view(torch.uint8).fill_(INT_POISON)
+        flat.view(torch.uint8).fill_(INT_POISON if poison is None else poison)
 
 
 def guard_elems(shape, dtype) -> int:
@@ -77,12 +82,18 @@ def guarded(shape, dtype, device="cpu", fill=None, values=None, name: str = "", 
     ``isfinite(view).all()``).  ``check()`` raises :class:`GuardError` if either guard differs
     from its saved copy.  ``poison``: a finite value for the guards of a floating-point tensor
     instead of NaN (max-reductions, see the module docstring); an output's interior stays NaN.
+    For a 1-byte tensor ``poison`` is a byte value (``BYTE_NAN`` for fp8 / E8M0 storage) that
+    replaces ``0xA5`` in the guards and in an output's interior.
     ``check.flat`` / ``check.start`` / ``check.numel`` give the whole buffer and the interior's
     element range in it (tests extend a view into a guard with them).
     """
     shape = tuple(int(s) for s in shape)
     item = torch.empty(0, dtype=dtype).element_size()
     n = math.prod(shape)
+    if poison is not None and not dtype.is_floating_point:
+        if item != 1 or int(poison) != poison or not 0 <= poison <= 0xFF:
+            raise ValueError(f"guarded: poison {poison!r} for {dtype}: a byte value for a 1-byte tensor only")
+        poison = int(poison)
     g = guard_elems(shape, dtype)
     flat = torch.empty(2 * g + n + ALIGN // item, dtype=dtype, device=device)
     lead = (-flat.data_ptr()) % ALIGN
@@ -94,7 +105,7 @@ def guarded(shape, dtype, device="cpu", fill=None, values=None, name: str = "", 
         view.copy_(values.to(dtype).reshape(shape))
     elif fill is not None:
         view.fill_(fill)
-    elif poison is not None:
+    elif poison is not None and dtype.is_floating_point:
         _poison_(view)
     assert view.is_contiguous() and view.storage_offset() > 0 and view.data_ptr() % ALIGN == 0
     iv = _INT_VIEW[item]

@@ -26,12 +26,11 @@ rows on both sides.
 NaN cannot show an out-of-tensor tap of a max-reduction (``fmaxf`` drops it), so the max-pool
 cases run a second time with +3e38 in the guards and gap channels: it would win every maximum.
 """
-import dataclasses
-
 import pytest
 import torch
 import torch.nn.functional as F
 
+from guard_ops import Operands, _bits, run_both  # noqa: F401  (shared with test_gpu_guard_transformer.py)
 from kernel_guard import GuardError, guarded
 
 pytestmark = pytest.mark.gpu
@@ -52,96 +51,6 @@ def _nhwc(x_nchw):
 
 def _nchw(x_nhwc):
     return x_nhwc.permute(0, 3, 1, 2)
-
-
-def _bits(t):
-    t = t.contiguous()
-    return t.view({1: torch.uint8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
-
-
-class Operands:
-    """Tensor factory of one run: plain (fresh tensors) or guarded (views between NaN guards)."""
-
-    def __init__(self, on: bool, poison=None):
-        self.on, self.checks, self.poison = on, [], poison
-
-    @property
-    def gap(self):
-        """What the gap channels of a sliced input hold: zero (plain) or the poison (guarded)."""
-        return 0.0 if not self.on else NAN if self.poison is None else self.poison
-
-    def _guard(self, shape, dtype, values, name):
-        view, check = guarded(shape, dtype, DEV, values=values, name=name,
-                              poison=self.poison if dtype.is_floating_point else None)
-        self.checks.append(check)
-        return view
-
-    def inp(self, values, name="input"):
-        """An input holding ``values`` (CPU or device tensor)."""
-        if not self.on:
-            return values.to(DEV).contiguous().clone()
-        return self._guard(values.shape, values.dtype, values.to(DEV), name)
-
-    def inp_slice(self, values, pitch, c0, name="input slice"):
-        """``values`` [..., C] as channels [c0, c0 + C) of a [..., pitch] buffer (ld > C).  The
-        gap channels are zero in the plain run (as the other test files have them) and poison in
-        the guarded run."""
-        C = values.shape[-1]
-        wide = torch.full((*values.shape[:-1], pitch), self.gap, dtype=values.dtype)
-        wide[..., c0:c0 + C] = values
-        return self.inp(wide, name)[..., c0:c0 + C]
-
-    def out(self, shape, dtype=BF16, name="output"):
-        """An output: NaN (floating point) in both runs, so an unwritten element is non-finite."""
-        if not self.on:
-            return torch.full(shape, NAN, dtype=dtype, device=DEV) if dtype.is_floating_point else \
-                torch.zeros(shape, dtype=dtype, device=DEV)
-        return self._guard(shape, dtype, None, name)
-
-    def spec(self, spec, name="spec"):
-        """``spec`` with its weight and bias swapped for guarded copies: a NEW ConvSpec, so every
-        derived image (patch / patchw / rows / exp / stem images) is re-derived from them."""
-        if not self.on:
-            return dataclasses.replace(spec)
-        return dataclasses.replace(spec, weight=self.inp(spec.weight, name + ".weight"),
-                                   bias=None if spec.bias is None else self.inp(spec.bias, name + ".bias"))
-
-    def check(self):
-        for c in self.checks:
-            c()
-
-
-def run_both(case, poison=None):
-    """``case(ops) -> tensor | tuple of tensors``: run plain and guarded, assert 1-3, return the
-    plain outputs (for assertion 4, the caller's).  ``poison``: a finite value instead of NaN in
-    the guards and gap channels (max-reductions)."""
-    plain_ops = Operands(False)
-    plain = case(plain_ops)
-    torch.cuda.synchronize()
-    ops = Operands(True, poison)
-    from aiko_services_amd.ops import conv as C
-    saved = dict(C._ZERO)                   # the LDS-DMA kernels' zero page is an operand too
-    try:
-        dev = torch.device(DEV, torch.cuda.current_device())
-        C._ZERO[dev] = ops.inp(torch.zeros(32, dtype=BF16), "zero page")
-        guard = case(ops)
-        torch.cuda.synchronize()
-    finally:
-        C._ZERO.clear()
-        C._ZERO.update(saved)
-    single = not isinstance(plain, (tuple, list))
-    plain, guard = ((plain,), (guard,)) if single else (tuple(plain), tuple(guard))
-    assert ops.checks, "the guarded run allocated no guarded tensor"
-    ops.check()                                                                   # 1
-    for i, t in enumerate(guard):                                                 # 2
-        if t.dtype.is_floating_point:
-            bad = (~torch.isfinite(t.float())).sum().item()
-            assert bad == 0, f"guarded output {i}: {bad} non-finite element(s) (poison consumed or unwritten)"
-    for i, (p, t) in enumerate(zip(plain, guard)):                                # 3
-        if not torch.equal(_bits(p), _bits(t)):
-            n = (_bits(p) != _bits(t)).sum().item()
-            raise AssertionError(f"output {i}: {n} element(s) differ between the plain and the guarded run")
-    return plain[0] if single else plain
 
 
 # ---- the helper on the device --------------------------------------------------------------------

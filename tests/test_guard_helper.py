@@ -3,7 +3,8 @@ one-element change on either side of the interior is reported with its side and 
 import pytest
 import torch
 
-from kernel_guard import ALIGN, GuardError, guard_elems, guarded
+from guard_ops import ROW_BOUND, row_err
+from kernel_guard import ALIGN, BYTE_NAN, GuardError, guard_elems, guarded
 
 DTYPES = [torch.bfloat16, torch.float32, torch.uint8]
 SHAPES = [(2, 9, 11, 24), (37, 1000), (3, 5, 7, 3), (5,)]
@@ -111,3 +112,100 @@ def test_first_difference_wins():
     with pytest.raises(GuardError) as e:
         check()
     assert (e.value.side, e.value.offset) == ("before", -5)
+
+
+# ---- byte poison for fp8 / E8M0 storage -----------------------------------------------------------
+
+def test_byte_poison_is_nan_as_e4m3_and_as_e8m0():
+    assert BYTE_NAN == 0xFF
+    b = torch.tensor([BYTE_NAN], dtype=torch.uint8)
+    assert torch.isnan(b.view(torch.float8_e4m3fn).float()).all()          # S.1111.111
+    a5 = torch.tensor([0xA5], dtype=torch.uint8)
+    assert torch.isfinite(a5.view(torch.float8_e4m3fn).float()).all()      # the default poison: a number
+    # E8M0 has one NaN, 0xFF (OCP MX v1.0); 0xA5 would be the scale 2^38 — torch has no such dtype
+    # on every build, so this is the format's definition, not a conversion
+    assert BYTE_NAN == 2 ** 8 - 1 and 0xA5 - 127 == 38
+
+
+@pytest.mark.parametrize("shape", [(37, 1000), (3, 128, 4), (5,)])
+def test_byte_poison_fills_guards_and_output_interior(shape):
+    out, check = guarded(shape, torch.uint8, poison=BYTE_NAN)
+    assert (check.flat == 0xFF).all() and (out == 0xFF).all()              # guards and interior
+    assert out.is_contiguous() and out.data_ptr() % ALIGN == 0
+    check()
+    vals = torch.arange(out.numel()).reshape(shape) % 200
+    inp, check = guarded(shape, torch.uint8, values=vals, poison=BYTE_NAN)
+    flat, s, n = check.flat, check.start, check.numel
+    assert torch.equal(inp, vals.to(torch.uint8))
+    assert (flat[:s] == 0xFF).all() and (flat[s + n:] == 0xFF).all()
+    filled, _ = guarded(shape, torch.uint8, fill=127, poison=BYTE_NAN)
+    assert (filled == 127).all()
+    default, c = guarded(shape, torch.uint8)                               # unchanged: 0xA5
+    assert (c.flat == 0xA5).all()
+
+
+@pytest.mark.parametrize("side,offset", [("before", -1), ("after", 0), ("after", 700)])
+def test_byte_poison_change_is_reported(side, offset):
+    view, check = guarded((3, 128, 4), torch.uint8, fill=127, poison=BYTE_NAN, name="scales")
+    at = check.start + offset if side == "before" else check.start + check.numel + offset
+    check.flat[at] = 0xA5                                                  # 0xFF -> the default poison
+    with pytest.raises(GuardError) as e:
+        check()
+    assert (e.value.side, e.value.offset) == (side, offset) and "scales" in str(e.value)
+    assert (view == 127).all()
+
+
+@pytest.mark.parametrize("dtype,poison", [(torch.int32, 0xFF), (torch.int16, 0xFF), (torch.uint8, 256),
+                                          (torch.uint8, -1), (torch.uint8, 1.5)])
+def test_byte_poison_is_for_one_byte_tensors_only(dtype, poison):
+    with pytest.raises(ValueError):
+        guarded((4, 8), dtype, poison=poison)
+
+
+# ---- the per-row metric ----------------------------------------------------------------------------
+
+def _rel(a, b):                                     # the whole-tensor number of test_gpu_transformer.py
+    a, b = a.float(), b.float()
+    return ((a - b).norm() / (b.norm() + 1e-12)).item()
+
+
+def test_row_err_basics():
+    ref = torch.tensor([[3.0, 4.0], [0.0, 0.0], [1.0, 0.0]])
+    assert row_err(ref.clone(), ref) == 0.0
+    y = ref.clone()
+    y[0, 0] = 3.5                                                          # 0.5 / 5
+    assert abs(row_err(y, ref) - 0.1) < 1e-12
+    y = ref.clone()
+    y[1, 1] = 1e-30                                                        # a zero row is compared exactly
+    assert row_err(y, ref) == float("inf")
+    y = ref.clone()
+    y[2, 1] = float("nan")
+    assert row_err(y, ref) == float("inf")
+    assert row_err(ref.to(torch.bfloat16), ref) == 0.0                     # any dtype in, fp64 inside
+
+
+def test_row_err_flags_what_the_whole_tensor_norm_lets_through():
+    """A GEMM output at the shape of test_gemm_fp8 (333 x 384, K = 768, weights / 30, the Whisper
+    model's bias scale 0.02), rounded to bf16 as a kernel would.  One row off by 5 % and a missing
+    bias on the last 5 rows (a tail the size of a partial tile) both stay under the whole-tensor
+    ``_rel < 5e-3`` of the existing tests; the per-row bound 2^-8 flags both, and passes the clean
+    output, whose rows carry one bf16 rounding: at most 2^-8 of an element (half an ulp of 8
+    significand bits), about 2^-9 of a row's norm."""
+    g = torch.Generator().manual_seed(0)
+    M, N, K = 333, 384, 768
+    x = torch.randn(M, K, generator=g, dtype=torch.float64)
+    w = torch.randn(N, K, generator=g, dtype=torch.float64) / 30
+    bias = 0.02 * torch.randn(N, generator=g, dtype=torch.float64)
+    ref = x @ w.T + bias
+    clean = ref.to(torch.bfloat16)
+    assert ROW_BOUND == 2.0 ** -8
+    assert 2.0 ** -10 < row_err(clean, ref) < 0.6 * ROW_BOUND
+    scaled = clean.clone()
+    scaled[200] = (ref[200] * 1.05).to(torch.bfloat16)
+    assert _rel(scaled, ref) < 5e-3                                        # the old bound: passes
+    assert row_err(scaled, ref) > ROW_BOUND                                # the new one: flagged
+    assert 0.045 < row_err(scaled, ref) < 0.055
+    nobias = clean.clone()
+    nobias[M - 5:] = (ref[M - 5:] - bias).to(torch.bfloat16)
+    assert _rel(nobias, ref) < 5e-3
+    assert row_err(nobias, ref) > ROW_BOUND
