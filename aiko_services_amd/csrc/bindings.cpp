@@ -75,6 +75,9 @@ int aiko_draw_detections(const void* frames, void* out, const float* det, const 
                          const float* scores, const void* names, const void* font, const void* palette, int B, int H,
                          int W, int max_det, int K, int C, int L, int G, int gh, int gw, int P, int t, int s,
                          float margin, int show_score, hipStream_t stream);
+int aiko_redact_detections(const void* frames, void* out, const float* det, const int* count, const int* labels,
+                           const void* select, int B, int H, int W, int max_det, int K, int C, int mode, int block,
+                           int fill_rgb, float margin, hipStream_t stream);
 int aiko_yuv_to_rgb_u8(const void* raw, void* out, int B, int H, int W, int fmt, const float* coef, int half,
                        hipStream_t stream);
 int aiko_rgb_to_yuv_u8(const void* rgb, void* out, int B, int H, int W, int fmt, const float* coef, int half,
@@ -1001,6 +1004,69 @@ void draw_detections_out(const at::Tensor& frames, const at::Tensor& det, const 
                "draw_detections");
 }
 
+// out <- frames with the pixels inside the rects of det[b, i] (i < min(count[b], k), coordinates
+// finite, class selected) replaced by the frame's mosaic (mode 0, block x block cells) or by
+// fill_rgb = R | G << 8 | B << 16 (mode 1); slot b*k + i of labels overrides the detector's class,
+// select[class] != 0 selects a class (no table: every class).  out may be frames itself (in place)
+void redact_detections_out(const at::Tensor& frames, const at::Tensor& det, const at::Tensor& count, int64_t k,
+                           const c10::optional<at::Tensor>& labels, const c10::optional<at::Tensor>& select,
+                           int64_t mode, int64_t block, int64_t fill_rgb, double margin, at::Tensor& out) {
+  check_cuda(frames, "frames");
+  check_cuda(det, "det");
+  check_cuda(count, "count");
+  check_cuda(out, "out");
+  TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 4 && frames.size(3) == 3 &&
+                  frames.is_contiguous() && frames.numel() >= 3,
+              "aiko.redact_detections_out: frames uint8 [B, H, W, 3] contiguous required");
+  const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2);
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(0) == B && det.size(2) == 6 &&
+                  det.is_contiguous(),
+              "aiko.redact_detections_out: det fp32 [B, max_det, 6] contiguous required");
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 && count.size(0) == B && count.is_contiguous(),
+              "aiko.redact_detections_out: count int32 [B] required");
+  const int64_t max_det = det.size(1);
+  TORCH_CHECK(k >= 1 && k <= max_det, "aiko.redact_detections_out: 1 <= k <= max_det (", max_det, ") required, got ",
+              k);
+  const int* lp = nullptr;
+  const void* sp = nullptr;
+  int64_t C = 0;
+  if (labels.has_value()) {
+    check_cuda(*labels, "labels");
+    TORCH_CHECK(labels->scalar_type() == at::kInt && labels->dim() == 1 && labels->size(0) == B * k &&
+                    labels->is_contiguous(),
+                "aiko.redact_detections_out: labels int32 [B*k] required");
+    lp = labels->data_ptr<int>();
+  }
+  if (select.has_value()) {
+    check_cuda(*select, "select");
+    TORCH_CHECK(select->scalar_type() == at::kByte && select->dim() == 1 && select->size(0) >= 1 &&
+                    select->size(0) < (1 << 24) && select->is_contiguous(),
+                "aiko.redact_detections_out: select uint8 [C] contiguous with C >= 1 required");
+    sp = select->data_ptr();
+    C = select->size(0);
+  }
+  TORCH_CHECK(mode == 0 || mode == 1, "aiko.redact_detections_out: mode 0 (pixelate) or 1 (fill) required, got ", mode);
+  TORCH_CHECK(block == 4 || block == 8 || block == 16 || block == 32,
+              "aiko.redact_detections_out: block in {4, 8, 16, 32} required, got ", block);
+  TORCH_CHECK(fill_rgb >= 0 && fill_rgb <= 0xffffff,
+              "aiko.redact_detections_out: fill components 0..255 (packed R | G << 8 | B << 16) required, got ",
+              fill_rgb);
+  TORCH_CHECK(margin >= 0.0 && margin <= 3.0e38, "aiko.redact_detections_out: a finite margin >= 0 required");
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.sizes() == frames.sizes() && out.is_contiguous(),
+              "aiko.redact_detections_out: out uint8 [B, H, W, 3] contiguous, the shape of frames, required");
+  const auto fp = reinterpret_cast<uintptr_t>(frames.data_ptr()), op = reinterpret_cast<uintptr_t>(out.data_ptr());
+  const uintptr_t nbytes = (uintptr_t)frames.numel();
+  TORCH_CHECK(fp == op || fp + nbytes <= op || op + nbytes <= fp,
+              "aiko.redact_detections_out: out overlaps frames without being the same tensor");
+  TORCH_CHECK(B <= 65535 && (H + 31) / 32 <= 65535 && H <= (1 << 24) && W <= (1 << 24),
+              "aiko.redact_detections_out: B = ", B, ", H = ", H, ", W = ", W,
+              " exceed the grid limit (65535 frames, 65535 tile rows of 32, side <= 2^24)");
+  check_launch(aiko_redact_detections(frames.data_ptr(), out.data_ptr(), det.data_ptr<float>(), count.data_ptr<int>(),
+                                      lp, sp, B, H, W, max_det, k, C, mode, block, fill_rgb, (float)margin,
+                                      cur_stream()),
+               "redact_detections");
+}
+
 // out [B, H, W, 3] <- raw [B, frame_bytes] YUV frames, tightly packed.  format: 0 nv12, 1 i420,
 // 2 i444, 3 yuyv; coeffs: yoff, ygain, rv, gu, gv, bu; round_mode: 0 rint, 1 add half and truncate
 void yuv_to_rgb_out(const at::Tensor& raw, int64_t height, int64_t width, int64_t format,
@@ -1814,6 +1880,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("resize_u8_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("roi_crop_out(Tensor frames, Tensor det, Tensor count, int k, float margin, Tensor(a!) crops, Tensor(b!) rois) -> ()");
   m.def("draw_detections_out(Tensor frames, Tensor det, Tensor count, int k, Tensor? labels, Tensor? scores, Tensor names, Tensor font, Tensor palette, int glyph_width, int thickness, int text_scale, float margin, bool show_score, Tensor(a!) out) -> ()");
+  m.def("redact_detections_out(Tensor frames, Tensor det, Tensor count, int k, Tensor? labels, Tensor? select, int mode, int block, int fill_rgb, float margin, Tensor(a!) out) -> ()");
   m.def("yuv_to_rgb_out(Tensor raw, int height, int width, int format, float[] coeffs, int round_mode, Tensor(a!) out) -> ()");
   m.def("rgb_to_yuv_out(Tensor rgb, int fmt, float[] coeffs, int round, Tensor(a!) out) -> ()");
   m.def("batchnorm_out(Tensor x, Tensor scale, Tensor shift, Tensor(a!) y, int act) -> ()");
@@ -1867,6 +1934,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("resize_u8_out", &resize_u8_out);
   m.impl("roi_crop_out", &roi_crop_out);
   m.impl("draw_detections_out", &draw_detections_out);
+  m.impl("redact_detections_out", &redact_detections_out);
   m.impl("yuv_to_rgb_out", &yuv_to_rgb_out);
   m.impl("rgb_to_yuv_out", &rgb_to_yuv_out);
   m.impl("batchnorm_out", &batchnorm_out);

@@ -239,6 +239,58 @@ def draw_detections_ref(frames: torch.Tensor, det: torch.Tensor, count: torch.Te
     return out
 
 
+# ---- detection redaction --------------------------------------------------------------------
+
+def redact_detections_ref(frames: torch.Tensor, det: torch.Tensor, count: torch.Tensor, k: int, *,
+                          mode: str = "pixelate", block: int = 16, fill=(0, 0, 0), margin: float = 0.0,
+                          select: torch.Tensor | None = None, labels: torch.Tensor | None = None) -> torch.Tensor:
+    """``ops.redact.redact_detections`` with torch on the CPU, from the rule in that module's
+    docstring: per frame a boolean coverage mask, the union of the rects (:func:`roi_rects_ref`) of
+    the used and selected rows, and — for ``pixelate`` — the frame's ``block`` x ``block`` cell
+    means ``(2*S + n) // (2*n)`` in int64, spread back over their cells.  Returns a new uint8
+    ``[B, H, W, 3]`` tensor."""
+    if mode not in ("pixelate", "fill"):
+        raise ValueError(f"redact_detections_ref: unknown mode {mode!r}")
+    if int(block) not in (4, 8, 16, 32):
+        raise ValueError(f"redact_detections_ref: block in {{4, 8, 16, 32}} required, got {block}")
+    frames, det, count = frames.cpu(), det.cpu().to(torch.float32), count.cpu()
+    B, H, W, _ = frames.shape
+    bs = int(block)
+    rects = roi_rects_ref(det, count, k, (H, W), margin).view(B, k, 4).tolist()
+    out = frames.clone()
+    for b in range(B):
+        covered = torch.zeros(H, W, dtype=torch.bool)
+        for i in range(k):
+            X0, Y0, X1, Y1 = rects[b][i]
+            if X1 <= X0:
+                continue
+            if select is not None:
+                if labels is not None:
+                    c = int(labels[b * k + i])
+                else:
+                    cf = float(det[b, i, 5])
+                    c = 0 if cf != cf else int(min(max(cf, -2.0 ** 31), 2.0 ** 31 - 1))
+                if not (0 <= c < select.shape[0] and int(select[c]) != 0):
+                    continue
+            covered[Y0:Y1, X0:X1] = True
+        if not bool(covered.any()):
+            continue
+        if mode == "fill":
+            colour = torch.tensor([int(c) for c in fill], dtype=torch.uint8).expand(H, W, 3)
+        else:
+            ch, cw = -(-H // bs), -(-W // bs)
+            padded = torch.zeros(ch * bs, cw * bs, 3, dtype=torch.int64)
+            padded[:H, :W] = frames[b].to(torch.int64)
+            S = padded.view(ch, bs, cw, bs, 3).sum((1, 3))                      # [ch, cw, 3]
+            ny = (H - torch.arange(ch) * bs).clamp(max=bs)                     # in-frame rows / columns
+            nx = (W - torch.arange(cw) * bs).clamp(max=bs)
+            n = (ny[:, None] * nx[None, :])[..., None]
+            mean = (2 * S + n) // (2 * n)
+            colour = mean.repeat_interleave(bs, 0).repeat_interleave(bs, 1)[:H, :W].to(torch.uint8)
+        out[b][covered] = colour[covered]
+    return out
+
+
 # ---- YUV ingest -----------------------------------------------------------------------------
 
 def yuv_planes_ref(raw: torch.Tensor, height: int, width: int, fmt: str):
