@@ -88,6 +88,9 @@ int aiko_track_detections(const float* det, const int* count, const float* boxes
                           float* boxes_out, int* meta_out, int* issued_out, int* ids, int* hits, int* labels, int B,
                           int max_det, int K, int T, float thr, int max_age, float min_score, int class_aware,
                           int label_mod, hipStream_t stream);
+int aiko_motion_detect(const void* frames, const int* bg, const int* seen, int* bg_out, int* seen_out, float* det,
+                       int* count, void* mask, int* cells, int B, int H, int W, int cell, int threshold,
+                       int learn_shift, int learn_moving, int warmup, int min_cells, int max_det, hipStream_t stream);
 int aiko_batchnorm(const void* x, void* y, const float* scale, const float* shift, long P, int C, int ldx,
                    int ldy, int act, hipStream_t stream);
 int aiko_upsample2x(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy,
@@ -1435,6 +1438,84 @@ void track_detections_out(const at::Tensor& det, const at::Tensor& count, const 
                "track_detections");
 }
 
+// One motion-detection step (motion_ops.hip; the rule is in ops/motion.py): frames [B, H, W, 3] and
+// the state bg [B, Gh, Gw] / seen [B] -> the next state in bg_out / seen_out, the moving regions as
+// detector rows in det [B, max_det, 6] / count [B], the moving cells in mask [B, Gh, Gw] and their
+// number in cells [B].  Two launches on the current stream
+void motion_detect_out(const at::Tensor& frames, const at::Tensor& bg, const at::Tensor& seen, int64_t cell,
+                       int64_t threshold, int64_t learn_shift, bool learn_moving, int64_t warmup, int64_t min_cells,
+                       at::Tensor& bg_out, at::Tensor& seen_out, at::Tensor& det, at::Tensor& count, at::Tensor& mask,
+                       at::Tensor& cells) {
+  const at::Tensor* ins[3] = {&frames, &bg, &seen};
+  const char* in_names[3] = {"frames", "bg", "seen"};
+  const at::Tensor* outs[6] = {&bg_out, &seen_out, &det, &count, &mask, &cells};
+  const char* out_names[6] = {"bg_out", "seen_out", "det", "count", "mask", "cells"};
+  for (int i = 0; i < 3; ++i) check_cuda(*ins[i], in_names[i]);
+  for (int o = 0; o < 6; ++o) check_cuda(*outs[o], out_names[o]);
+  for (int i = 1; i < 3; ++i)
+    TORCH_CHECK(ins[i]->device() == frames.device(), "aiko.motion_detect_out: tensors on different devices");
+  for (int o = 0; o < 6; ++o)
+    TORCH_CHECK(outs[o]->device() == frames.device(), "aiko.motion_detect_out: tensors on different devices");
+  TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 4 && frames.size(3) == 3 &&
+                  frames.is_contiguous() && frames.numel() >= 3,
+              "aiko.motion_detect_out: frames uint8 [B, H, W, 3] contiguous required");
+  const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2);
+  TORCH_CHECK(cell == 8 || cell == 16 || cell == 32, "aiko.motion_detect_out: cell in {8, 16, 32} required, got ",
+              cell);
+  TORCH_CHECK(B <= 65535 && (H + 31) / 32 <= 65535 && H <= (1 << 24) && W <= (1 << 24),
+              "aiko.motion_detect_out: B = ", B, ", H = ", H, ", W = ", W,
+              " exceed the grid limit (65535 frames, 65535 tile rows of 32, side <= 2^24)");
+  const int64_t Gh = (H + cell - 1) / cell, Gw = (W + cell - 1) / cell;
+  TORCH_CHECK(Gh <= 255 && Gw <= 255 && Gh * Gw <= 16384, "aiko.motion_detect_out: a grid of ", Gh, " x ", Gw,
+              " cells exceeds the limits (255 rows, 255 columns, 16384 cells): choose a larger cell");
+  TORCH_CHECK(threshold >= 0 && threshold <= 255, "aiko.motion_detect_out: 0 <= threshold <= 255 required, got ",
+              threshold);
+  TORCH_CHECK(learn_shift >= 0 && learn_shift <= 8, "aiko.motion_detect_out: 0 <= learn_shift <= 8 required, got ",
+              learn_shift);
+  TORCH_CHECK(warmup >= 1 && warmup <= INT_MAX, "aiko.motion_detect_out: warmup >= 1 required, got ", warmup);
+  TORCH_CHECK(min_cells >= 1 && min_cells <= INT_MAX, "aiko.motion_detect_out: min_cells >= 1 required, got ",
+              min_cells);
+  auto is_state = [&](const at::Tensor& g, const at::Tensor& s) {
+    return g.scalar_type() == at::kInt && g.dim() == 3 && g.size(0) == B && g.size(1) == Gh && g.size(2) == Gw &&
+           g.is_contiguous() && s.scalar_type() == at::kInt && s.dim() == 1 && s.size(0) == B && s.is_contiguous();
+  };
+  TORCH_CHECK(is_state(bg, seen), "aiko.motion_detect_out: state bg int32 [B, Gh, Gw], seen int32 [B] contiguous "
+              "required, B = ", B, ", Gh = ", Gh, ", Gw = ", Gw);
+  TORCH_CHECK(is_state(bg_out, seen_out), "aiko.motion_detect_out: state_out bg int32 [B, Gh, Gw], seen int32 [B] "
+              "contiguous required, B = ", B, ", Gh = ", Gh, ", Gw = ", Gw);
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(0) == B && det.size(2) == 6 &&
+                  det.is_contiguous(),
+              "aiko.motion_detect_out: det fp32 [B, max_det, 6] contiguous required");
+  const int64_t max_det = det.size(1);
+  TORCH_CHECK(max_det >= 1 && max_det <= 64, "aiko.motion_detect_out: 1 <= max_det <= 64 required, got ", max_det);
+  for (const at::Tensor* t : {&count, &cells})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1 && t->size(0) == B && t->is_contiguous(),
+                "aiko.motion_detect_out: count and cells int32 [B] contiguous required");
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.dim() == 3 && mask.size(0) == B && mask.size(1) == Gh &&
+                  mask.size(2) == Gw && mask.is_contiguous(),
+              "aiko.motion_detect_out: mask uint8 [B, Gh, Gw] = [", B, ", ", Gh, ", ", Gw, "] contiguous required");
+  // no output may overlap an input or another output
+  auto overlap = [](const at::Tensor& x, const at::Tensor& y) {
+    const auto xp = reinterpret_cast<uintptr_t>(x.data_ptr()), yp = reinterpret_cast<uintptr_t>(y.data_ptr());
+    const uintptr_t xn = x.numel() * x.element_size(), yn = y.numel() * y.element_size();
+    return xn > 0 && yn > 0 && xp < yp + yn && yp < xp + xn;
+  };
+  for (int o = 0; o < 6; ++o) {
+    for (int i = 0; i < 3; ++i)
+      TORCH_CHECK(!overlap(*outs[o], *ins[i]), "aiko.motion_detect_out: ", out_names[o], " and ", in_names[i],
+                  " overlap");
+    for (int p = 0; p < o; ++p)
+      TORCH_CHECK(!overlap(*outs[o], *outs[p]), "aiko.motion_detect_out: ", out_names[o], " and ", out_names[p],
+                  " overlap");
+  }
+  check_launch(aiko_motion_detect(frames.data_ptr(), bg.data_ptr<int>(), seen.data_ptr<int>(), bg_out.data_ptr<int>(),
+                                  seen_out.data_ptr<int>(), det.data_ptr<float>(), count.data_ptr<int>(),
+                                  mask.data_ptr(), cells.data_ptr<int>(), (int)B, (int)H, (int)W, (int)cell,
+                                  (int)threshold, (int)learn_shift, learn_moving ? 1 : 0, (int)warmup, (int)min_cells,
+                                  (int)max_det, cur_stream()),
+               "motion_detect");
+}
+
 void avgpool_out(const at::Tensor& x, at::Tensor& y) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -1898,6 +1979,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("mean_rows_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("window_shift_out(Tensor src, Tensor chunk, Tensor(a!) dst) -> ()");
   m.def("track_detections_out(Tensor det, Tensor count, Tensor boxes, Tensor meta, Tensor issued, int k, float iou, int max_age, float min_score, bool class_aware, int label_mod, Tensor(a!) boxes_out, Tensor(b!) meta_out, Tensor(c!) issued_out, Tensor(d!) ids, Tensor(e!) hits, Tensor(f!) labels) -> ()");
+  m.def("motion_detect_out(Tensor frames, Tensor bg, Tensor seen, int cell, int threshold, int learn_shift, bool learn_moving, int warmup, int min_cells, Tensor(a!) bg_out, Tensor(b!) seen_out, Tensor(c!) det, Tensor(d!) count, Tensor(e!) mask, Tensor(f!) cells) -> ()");
   m.def("resample_out(Tensor pcm, Tensor hist, Tensor filt, int L, int M, Tensor(a!) out, Tensor(b!) hist_out) -> ()");
   m.def("zero_border_rows_(Tensor(a!) x, int rows) -> ()");
   m.def("sppf_pool_(Tensor(a!) cat, int c, int k) -> ()");
@@ -1945,6 +2027,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("window_shift_out", &window_shift_out);
   m.impl("resample_out", &resample_out);
   m.impl("track_detections_out", &track_detections_out);
+  m.impl("motion_detect_out", &motion_detect_out);
   m.impl("zero_border_rows_", &zero_border_rows_);
   m.impl("sppf_pool_", &sppf_pool_);
   m.impl("stem_pool_out", &stem_pool_out);

@@ -528,3 +528,79 @@ def track_ref(det: torch.Tensor, count: torch.Tensor, state, k: int, *, iou: flo
     out = [torch.from_numpy(x.astype(np.int32)).reshape(-1) for x in (ids, hits, labels)]
     return (*out, TrackState(torch.from_numpy(boxes), torch.from_numpy(meta.astype(np.int32)),
                              torch.from_numpy(issued.astype(np.int32))))
+
+
+# ---- motion detection -----------------------------------------------------------------------
+
+def motion_detect_ref(frames: torch.Tensor, state, *, cell: int = 16, threshold: int = 12, learn_shift: int = 4,
+                      learn_moving: bool = True, warmup: int = 1, min_cells: int = 2, max_det: int = 16):
+    """The definition of :func:`aiko_services_amd.ops.motion.motion_detect` on the CPU, in plain
+    loops over cells: ``(det, count, mask, cells, state_out)`` for uint8 ``frames`` ``[B, H, W, 3]``
+    and a ``MotionState``.  Integers are Python ints (the per-pixel luma and a cell's sum are numpy
+    int64), the components come from a breadth-first walk, the score is a Python float division
+    (fp64) rounded to fp32 once.  ``state`` is not modified."""
+    from collections import deque
+
+    import numpy as np
+
+    from .motion import MotionState, check_parameters, grid_shape
+    check_parameters(cell, threshold, learn_shift, warmup, min_cells, max_det)
+    f = frames.detach().cpu().numpy().astype(np.int64)
+    B, H, W, _ = f.shape
+    gh, gw = grid_shape(H, W, cell)
+    bg = state.bg.detach().cpu().numpy().astype(np.int64)
+    seen = state.seen.detach().cpu().numpy().astype(np.int64)
+    luma = (77 * f[..., 0] + 150 * f[..., 1] + 29 * f[..., 2] + 128) >> 8
+    half = (1 << (learn_shift - 1)) if learn_shift else 0
+    bg_out = np.zeros((B, gh, gw), np.int64)
+    seen_out = np.zeros(B, np.int64)
+    mask = np.zeros((B, gh, gw), np.uint8)
+    det = np.zeros((B, max_det, 6), np.float32)
+    count = np.zeros(B, np.int32)
+    cells = np.zeros(B, np.int32)
+    for b in range(B):
+        s = max(int(seen[b]), 0)
+        for gy in range(gh):
+            for gx in range(gw):
+                block = luma[b, gy * cell:min((gy + 1) * cell, H), gx * cell:min((gx + 1) * cell, W)]
+                S, n = int(block.sum()), block.size
+                cur = (32 * S + n) // (2 * n)
+                old = int(bg[b, gy, gx])
+                moving = s >= warmup and abs(cur - old) > 16 * threshold
+                if s == 0:
+                    new = cur
+                elif moving and not learn_moving:
+                    new = old
+                else:
+                    new = old + ((cur - old + half) >> learn_shift)      # Python's >> floors
+                bg_out[b, gy, gx] = new
+                mask[b, gy, gx] = 1 if moving else 0
+        seen_out[b] = min(s + 1, 2 ** 31 - 1)
+        cells[b] = int(mask[b].sum())
+        # components in raster order of their first cell: that cell's index is the label
+        done = np.zeros((gh, gw), bool)
+        found = []                                              # (area, label, cx0, cy0, cx1, cy1)
+        for gy in range(gh):
+            for gx in range(gw):
+                if not mask[b, gy, gx] or done[gy, gx]:
+                    continue
+                done[gy, gx] = True
+                todo, area, box = deque([(gy, gx)]), 0, [gx, gy, gx, gy]
+                while todo:
+                    y, x = todo.popleft()
+                    area += 1
+                    box = [min(box[0], x), min(box[1], y), max(box[2], x), max(box[3], y)]
+                    for ny in range(max(y - 1, 0), min(y + 2, gh)):
+                        for nx in range(max(x - 1, 0), min(x + 2, gw)):
+                            if mask[b, ny, nx] and not done[ny, nx]:
+                                done[ny, nx] = True
+                                todo.append((ny, nx))
+                if area >= min_cells:
+                    found.append((area, gy * gw + gx, *box))
+        found.sort(key=lambda c: (-c[0], c[1]))
+        for i, (area, _, cx0, cy0, cx1, cy1) in enumerate(found[:max_det]):
+            score = np.float32(area / ((cx1 - cx0 + 1) * (cy1 - cy0 + 1)))
+            det[b, i] = (cx0 * cell, cy0 * cell, min((cx1 + 1) * cell, W), min((cy1 + 1) * cell, H), score, 0)
+        count[b] = min(len(found), max_det)
+    return (torch.from_numpy(det), torch.from_numpy(count), torch.from_numpy(mask), torch.from_numpy(cells),
+            MotionState(torch.from_numpy(bg_out.astype(np.int32)), torch.from_numpy(seen_out.astype(np.int32))))
