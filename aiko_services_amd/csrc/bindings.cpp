@@ -91,6 +91,8 @@ int aiko_track_detections(const float* det, const int* count, const float* boxes
 int aiko_motion_detect(const void* frames, const int* bg, const int* seen, int* bg_out, int* seen_out, float* det,
                        int* count, void* mask, int* cells, int B, int H, int W, int cell, int threshold,
                        int learn_shift, int learn_moving, int warmup, int min_cells, int max_det, hipStream_t stream);
+int aiko_jpeg_encode(const void* raw, const void* tables, int header_len, void* workspace, void* stream, int* nbytes,
+                     int B, int H, int W, int fmt, long cap, int seg_cap, hipStream_t stream_);
 int aiko_batchnorm(const void* x, void* y, const float* scale, const float* shift, long P, int C, int ldx,
                    int ldy, int act, hipStream_t stream);
 int aiko_upsample2x(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy,
@@ -1516,6 +1518,58 @@ void motion_detect_out(const at::Tensor& frames, const at::Tensor& bg, const at:
                "motion_detect");
 }
 
+// Baseline JPEG (jpeg_ops.hip; the rule is in ops/jpeg.py): raw planar frames [B, frame_bytes] (fmt 1: i420,
+// 2: i444) -> one JFIF stream per frame in stream [B, cap], its length (-1: overflow) in nbytes [B].  tables is
+// ops.jpeg.device_tables' tensor (864 words, then header_len bytes of header); workspace holds an int32 and
+// seg_cap bytes per (frame, MCU row).  Two launches on the current stream
+void jpeg_encode_out(const at::Tensor& raw, int64_t height, int64_t width, int64_t fmt, const at::Tensor& tables,
+                     int64_t header_len, int64_t seg_cap, at::Tensor& stream, at::Tensor& nbytes,
+                     at::Tensor& workspace) {
+  const at::Tensor* ts[5] = {&raw, &tables, &stream, &nbytes, &workspace};
+  const char* names[5] = {"raw", "tables", "stream", "nbytes", "workspace"};
+  for (int i = 0; i < 5; ++i) check_cuda(*ts[i], names[i]);
+  for (int i = 1; i < 5; ++i)
+    TORCH_CHECK(ts[i]->device() == raw.device(), "aiko.jpeg_encode_out: tensors on different devices");
+  TORCH_CHECK(fmt == 1 || fmt == 2, "aiko.jpeg_encode_out: fmt 1 (i420) or 2 (i444) required, got ", fmt);
+  TORCH_CHECK(height >= 1 && height <= 65535 && width >= 1 && width <= 4096,
+              "aiko.jpeg_encode_out: 1 <= height <= 65535 and 1 <= width <= 4096 required, got ", height, " x ", width);
+  const int64_t H = height, W = width, mcu = fmt == 1 ? 16 : 8;
+  const int64_t my = (H + mcu - 1) / mcu;
+  const int64_t frame = fmt == 1 ? H * W + 2 * ((H + 1) / 2) * ((W + 1) / 2) : 3 * H * W;
+  TORCH_CHECK(raw.scalar_type() == at::kByte && raw.dim() == 2 && raw.size(1) == frame && raw.is_contiguous() &&
+                  raw.size(0) >= 1,
+              "aiko.jpeg_encode_out: raw uint8 [B, ", frame, "] contiguous required");
+  const int64_t B = raw.size(0);
+  TORCH_CHECK(B <= 65535, "aiko.jpeg_encode_out: B = ", B, " exceeds the grid limit (65535 frames)");
+  TORCH_CHECK(seg_cap >= 1 && seg_cap <= 96 * 1024, "aiko.jpeg_encode_out: 1 <= seg_cap <= 98304 required, got ",
+              seg_cap);
+  TORCH_CHECK(header_len >= 1 && tables.scalar_type() == at::kByte && tables.dim() == 1 && tables.is_contiguous() &&
+                  tables.numel() == 4 * 864 + header_len && reinterpret_cast<uintptr_t>(tables.data_ptr()) % 4 == 0,
+              "aiko.jpeg_encode_out: tables uint8 [3456 + header_len] contiguous, 4-byte aligned required");
+  TORCH_CHECK(stream.scalar_type() == at::kByte && stream.dim() == 2 && stream.size(0) == B && stream.size(1) >= 1 &&
+                  stream.size(1) <= INT_MAX && stream.is_contiguous(),
+              "aiko.jpeg_encode_out: stream uint8 [B, cap] contiguous required, 1 <= cap < 2^31");
+  TORCH_CHECK(nbytes.scalar_type() == at::kInt && nbytes.dim() == 1 && nbytes.size(0) == B && nbytes.is_contiguous(),
+              "aiko.jpeg_encode_out: nbytes int32 [B] contiguous required");
+  const int64_t need = B * my * (4 + seg_cap);
+  TORCH_CHECK(workspace.scalar_type() == at::kByte && workspace.dim() == 1 && workspace.is_contiguous() &&
+                  workspace.numel() >= need && reinterpret_cast<uintptr_t>(workspace.data_ptr()) % 4 == 0,
+              "aiko.jpeg_encode_out: workspace uint8 [>= ", need, "] contiguous, 4-byte aligned required");
+  // no output may overlap an input or another output
+  auto overlap = [](const at::Tensor& x, const at::Tensor& y) {
+    const auto xp = reinterpret_cast<uintptr_t>(x.data_ptr()), yp = reinterpret_cast<uintptr_t>(y.data_ptr());
+    const uintptr_t xn = x.numel() * x.element_size(), yn = y.numel() * y.element_size();
+    return xn > 0 && yn > 0 && xp < yp + yn && yp < xp + xn;
+  };
+  for (int o = 2; o < 5; ++o)
+    for (int p = 0; p < o; ++p)
+      TORCH_CHECK(!overlap(*ts[o], *ts[p]), "aiko.jpeg_encode_out: ", names[o], " and ", names[p], " overlap");
+  check_launch(aiko_jpeg_encode(raw.data_ptr(), tables.data_ptr(), (int)header_len, workspace.data_ptr(),
+                                stream.data_ptr(), nbytes.data_ptr<int>(), (int)B, (int)H, (int)W, (int)fmt,
+                                (long)stream.size(1), (int)seg_cap, cur_stream()),
+               "jpeg_encode");
+}
+
 void avgpool_out(const at::Tensor& x, at::Tensor& y) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -1980,6 +2034,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("window_shift_out(Tensor src, Tensor chunk, Tensor(a!) dst) -> ()");
   m.def("track_detections_out(Tensor det, Tensor count, Tensor boxes, Tensor meta, Tensor issued, int k, float iou, int max_age, float min_score, bool class_aware, int label_mod, Tensor(a!) boxes_out, Tensor(b!) meta_out, Tensor(c!) issued_out, Tensor(d!) ids, Tensor(e!) hits, Tensor(f!) labels) -> ()");
   m.def("motion_detect_out(Tensor frames, Tensor bg, Tensor seen, int cell, int threshold, int learn_shift, bool learn_moving, int warmup, int min_cells, Tensor(a!) bg_out, Tensor(b!) seen_out, Tensor(c!) det, Tensor(d!) count, Tensor(e!) mask, Tensor(f!) cells) -> ()");
+  m.def("jpeg_encode_out(Tensor raw, int height, int width, int fmt, Tensor tables, int header_len, int seg_cap, Tensor(a!) stream, Tensor(b!) nbytes, Tensor(c!) workspace) -> ()");
   m.def("resample_out(Tensor pcm, Tensor hist, Tensor filt, int L, int M, Tensor(a!) out, Tensor(b!) hist_out) -> ()");
   m.def("zero_border_rows_(Tensor(a!) x, int rows) -> ()");
   m.def("sppf_pool_(Tensor(a!) cat, int c, int k) -> ()");
@@ -2028,6 +2083,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("resample_out", &resample_out);
   m.impl("track_detections_out", &track_detections_out);
   m.impl("motion_detect_out", &motion_detect_out);
+  m.impl("jpeg_encode_out", &jpeg_encode_out);
   m.impl("zero_border_rows_", &zero_border_rows_);
   m.impl("sppf_pool_", &sppf_pool_);
   m.impl("stem_pool_out", &stem_pool_out);

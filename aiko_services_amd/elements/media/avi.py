@@ -25,7 +25,7 @@ from pathlib import Path
 
 import numpy as np
 
-__all__ = ["AviWriter", "iter_avi", "read_avi", "avi_info", "write_avi"]
+__all__ = ["AviWriter", "iter_avi", "jpeg_size", "read_avi", "avi_info", "write_avi"]
 
 _AVIF_HASINDEX = 0x10
 _AVIIF_KEYFRAME = 0x10
@@ -155,9 +155,22 @@ def read_avi(path) -> np.ndarray:
 
 # ---- writing ---------------------------------------------------------------------------------
 
+def jpeg_size(data) -> tuple:
+    """(height, width) of a JPEG file, from its frame header."""
+    data = bytes(data[:65536])
+    i = 2
+    while i + 9 <= len(data) and data[i] == 0xFF:
+        marker, length = data[i + 1], data[i + 2] << 8 | data[i + 3]
+        if 0xC0 <= marker <= 0xCF and marker not in (0xC4, 0xC8, 0xCC):
+            return data[i + 5] << 8 | data[i + 6], data[i + 7] << 8 | data[i + 8]
+        i += 2 + length
+    raise ValueError("no frame header in the JPEG data")
+
+
 class AviWriter:
     """``write(rgb)`` frames of one size into ``path``; ``codec`` ``"MJPG"`` (JPEG ``quality``)
-    or ``"raw"`` (uncompressed 24-bit DIB, lossless)."""
+    or ``"raw"`` (uncompressed 24-bit DIB, lossless).  ``write_jpeg(data)`` appends a frame that is
+    JPEG-coded already (``JpegEncode``'s, on the device) to an MJPG video."""
 
     def __init__(self, path, width: int, height: int, fps: float = 30.0, codec: str = "MJPG",
                  quality: int = 90):
@@ -208,7 +221,22 @@ class AviWriter:
             a = np.repeat(a[..., None], 3, axis=2)
         if a.shape[:2] != (self.h, self.w) or a.shape[2] != 3:
             raise ValueError(f"frame {a.shape} does not match the video's {self.h}x{self.w}x3")
-        cid, data = self._encode(np.ascontiguousarray(a.astype(np.uint8, copy=False)))
+        self._append(*self._encode(np.ascontiguousarray(a.astype(np.uint8, copy=False))))
+
+    def write_jpeg(self, data):
+        """Append an already coded frame (a complete JPEG file of the video's size: ``bytes`` or a uint8
+        array) as a ``00dc`` chunk, as it is.  MJPG only."""
+        if self.codec != "MJPG":
+            raise ValueError(f"coded JPEG frames go into an MJPG video, not codec {self.codec!r}")
+        data = bytes(data)
+        if data[:2] != b"\xff\xd8" or data[-2:] != b"\xff\xd9":
+            raise ValueError("not a JPEG frame: it does not run from SOI to EOI")
+        size = jpeg_size(data)
+        if size != (self.h, self.w):
+            raise ValueError(f"JPEG frame of {size[0]}x{size[1]} does not match the video's {self.h}x{self.w}")
+        self._append(b"00dc", data)
+
+    def _append(self, cid: bytes, data: bytes):
         off = self.f.tell() - (self._movi_at + 8)        # from the 'movi' fourcc
         self.f.write(cid + struct.pack("<I", len(data)) + data + (b"\0" if len(data) & 1 else b""))
         self.index.append((cid, off, len(data)))

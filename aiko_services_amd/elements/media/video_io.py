@@ -16,7 +16,7 @@ import numpy as np
 
 from ...pipeline.engine import PipelineElement
 from ...pipeline.stream import StreamEvent
-from .avi import AviWriter, iter_avi
+from .avi import AviWriter, iter_avi, jpeg_size
 from .common_io import DataSource, DataTarget, contains_all
 
 try:  # optional
@@ -303,14 +303,27 @@ class VideoWriteFile(DataTarget):
     ``.gif``, ``.y4m`` or ``.npy``; other suffixes need OpenCV.  ``rate``: frames per second.
     ``raw: true`` (``.y4m`` only) with ``format: i420 | i444``, ``height`` and ``width``: 1-D
     ``images`` are a frame's packed planes (``RgbToYuv`` then ``FrameDownload``) and are written
-    unconverted, ``C420jpeg`` or ``C444``; anything else is an error."""
+    unconverted, ``C420jpeg`` or ``C444``; ``raw: true`` with ``format: jpeg`` (``.avi`` only): 1-D
+    ``images`` are complete JPEG files (``JpegEncode`` then ``JpegResults``) and become the frames of
+    an MJPG video as they are, its size taken from the first (or from ``height`` and ``width``);
+    anything else is an error."""
 
     _RAW_CHROMA = {"i420": "420jpeg", "i444": "444"}
 
-    def _raw_writer(self, path, suffix):
-        """``(Y4MWriter, None)`` for ``raw: true``, or ``(None, diagnostic)``."""
+    def _raw_writer(self, path, suffix, first=None):
+        """``(writer, None)`` for ``raw: true``, or ``(None, diagnostic)``; ``first``: the first frame."""
         fmt = str(self.get_parameter("format", "")[0]).lower()
         height, width = self.get_parameter("height", None)[0], self.get_parameter("width", None)[0]
+        if fmt == "jpeg":
+            if suffix != ".avi":
+                return None, f"{path}: coded JPEG frames need a .avi file"
+            try:
+                if height is None or width is None:
+                    height, width = jpeg_size(np.asarray(first, np.uint8).tobytes())
+            except (ValueError, TypeError) as exc:
+                return None, f"{path}: {exc}"
+            rate, _ = self.get_parameter("rate", 30)
+            return AviWriter(path, int(width), int(height), float(rate), "MJPG"), None
         if suffix != ".y4m":
             return None, f"{path}: raw frames need a .y4m file"
         if fmt not in self._RAW_CHROMA:
@@ -340,7 +353,7 @@ class VideoWriteFile(DataTarget):
         suffix = Path(path).suffix.lower()
         raw = str(self.get_parameter("raw", False)[0]).lower() in ("true", "1", "yes")
         if raw and stream.variables["video_writer"] is None:
-            writer, diagnostic = self._raw_writer(path, suffix)
+            writer, diagnostic = self._raw_writer(path, suffix, images[0] if len(images) else None)
             if writer is None:
                 return StreamEvent.ERROR, {"diagnostic": diagnostic}
             stream.variables["video_writer"] = writer
@@ -348,7 +361,8 @@ class VideoWriteFile(DataTarget):
             arr = np.asarray(image).astype(np.uint8)
             if raw and arr.ndim == 1:
                 try:
-                    stream.variables["video_writer"].write_raw(arr)
+                    writer = stream.variables["video_writer"]
+                    (writer.write_jpeg if isinstance(writer, AviWriter) else writer.write_raw)(arr)
                 except ValueError as exc:
                     return StreamEvent.ERROR, {"diagnostic": str(exc)}
                 continue

@@ -604,3 +604,120 @@ def motion_detect_ref(frames: torch.Tensor, state, *, cell: int = 16, threshold:
         count[b] = min(len(found), max_det)
     return (torch.from_numpy(det), torch.from_numpy(count), torch.from_numpy(mask), torch.from_numpy(cells),
             MotionState(torch.from_numpy(bg_out.astype(np.int32)), torch.from_numpy(seen_out.astype(np.int32))))
+
+
+# ---- JPEG -------------------------------------------------------------------------------------
+
+def _jpeg_planes_ref(frame: torch.Tensor, fmt: str, H: int, W: int):
+    """The three component planes of one packed ``i420`` / ``i444`` frame, int64."""
+    ch, cw = ((H + 1) // 2, (W + 1) // 2) if fmt == "i420" else (H, W)
+    f = frame.to(torch.int64)
+    return [f[:H * W].view(H, W), f[H * W:H * W + ch * cw].view(ch, cw), f[H * W + ch * cw:].view(ch, cw)]
+
+
+def _jpeg_block_ref(plane: torch.Tensor, by: int, bx: int, M: torch.Tensor, q: torch.Tensor) -> list:
+    """The quantised coefficients, natural order, of the 8 x 8 block at (``by``, ``bx``) of ``plane``:
+    samples outside the plane are those at the clamped coordinates."""
+    ys = torch.arange(by, by + 8).clamp_(max=plane.shape[0] - 1)
+    xs = torch.arange(bx, bx + 8).clamp_(max=plane.shape[1] - 1)
+    x = plane[ys][:, xs] - 128
+    t = (M @ x + 1024) >> 11                                # columns; >> on int64 is arithmetic
+    c = (t @ M.T + 16384) >> 15                             # rows
+    v = torch.sign(c) * ((c.abs() + (q >> 1)) // q)
+    return v.clamp_(-1023, 1023).flatten().tolist()
+
+
+def jpeg_encode_ref(raw: torch.Tensor, height: int, width: int, fmt: str = "i420", quality: int = 90, *,
+                    cap: int | None = None, seg_cap: int | None = None, trace: list | None = None):
+    """``ops.jpeg.jpeg_encode`` on the CPU in plain loops, the rule of :mod:`~aiko_services_amd.ops.jpeg`
+    literally: uint8 ``[B, frame_bytes]`` -> ``(stream uint8 [B, cap], nbytes int32 [B])``.  An
+    overflowed frame has ``nbytes`` -1 and a row of zeros; the bytes past ``nbytes`` are zeros.
+    ``trace`` (a list) receives every coded symbol as ``(frame, MCU row, block in the row, "dc" | "ac",
+    symbol, value)``, ``value`` the DC difference or the coefficient (0 for ``ZRL`` and ``EOB``)."""
+    from . import jpeg as J
+    from .yuv import frame_bytes
+    mh, mw, nblk, my, mx = J.geometry(fmt, height, width)
+    H, W = int(height), int(width)
+    raw = raw.cpu()
+    if raw.dim() != 2 or raw.dtype != torch.uint8 or raw.shape[1] != frame_bytes(fmt, H, W):
+        raise ValueError(f"jpeg_encode_ref: uint8 [B, {frame_bytes(fmt, H, W)}] required, got {tuple(raw.shape)}")
+    head = J.header(fmt, H, W, quality)
+    dcap, dseg = J.capacities(fmt, H, W)
+    cap, seg_cap = dcap if cap is None else int(cap), dseg if seg_cap is None else int(seg_cap)
+    M = torch.tensor(J.DCT_MATRIX, dtype=torch.int64)
+    quant = [torch.tensor(t, dtype=torch.int64).view(8, 8) for t in J.quant_tables(quality)]
+    dc_codes = [J.huffman_codes(0x00), J.huffman_codes(0x01)]
+    ac_codes = [J.huffman_codes(0x10), J.huffman_codes(0x11)]
+    # (component, block row, block column) of an MCU's blocks, in coding order
+    layout = [(0, 0, 0), (0, 0, 1), (0, 1, 0), (0, 1, 1), (1, 0, 0), (2, 0, 0)] if fmt == "i420" else \
+        [(0, 0, 0), (1, 0, 0), (2, 0, 0)]
+    ysub = 2 if fmt == "i420" else 1                        # luma blocks per MCU side
+    B = raw.shape[0]
+    stream = torch.zeros(B, cap, dtype=torch.uint8)
+    nbytes = torch.empty(B, dtype=torch.int32)
+    for b in range(B):
+        planes = _jpeg_planes_ref(raw[b], fmt, H, W)
+        out, overflow = bytearray(head), False
+        for row in range(my):
+            acc, nacc, seg = 0, 0, bytearray()              # the bit buffer: nacc bits in acc
+
+            def put(code: int, length: int):
+                nonlocal acc, nacc
+                acc, nacc = acc << length | code, nacc + length
+                while nacc >= 8:
+                    byte = acc >> (nacc - 8) & 0xFF
+                    seg.append(byte)
+                    if byte == 0xFF:
+                        seg.append(0)
+                    nacc -= 8
+                acc &= (1 << nacc) - 1
+
+            def put_value(v: int, size: int):
+                if size:
+                    put(v if v >= 0 else v + (1 << size) - 1, size)
+
+            pred = [0, 0, 0]
+            for m in range(mx):
+                for k, (comp, sy, sx) in enumerate(layout):
+                    sub = ysub if comp == 0 else 1
+                    tq = 0 if comp == 0 else 1
+                    v = _jpeg_block_ref(planes[comp], (row * sub + sy) * 8, (m * sub + sx) * 8, M, quant[tq])
+                    z = [v[n] for n in J.ZIGZAG]
+                    blk = m * nblk + k
+                    diff, pred[comp] = z[0] - pred[comp], z[0]
+                    size = abs(diff).bit_length()
+                    put(*dc_codes[tq][size])
+                    put_value(diff, size)
+                    if trace is not None:
+                        trace.append((b, row, blk, "dc", size, diff))
+                    run = 0
+                    for i in range(1, 64):
+                        if z[i] == 0:
+                            run += 1
+                            continue
+                        while run > 15:
+                            put(*ac_codes[tq][0xF0])
+                            run -= 16
+                            if trace is not None:
+                                trace.append((b, row, blk, "ac", 0xF0, 0))
+                        size = abs(z[i]).bit_length()
+                        put(*ac_codes[tq][run << 4 | size])
+                        put_value(z[i], size)
+                        if trace is not None:
+                            trace.append((b, row, blk, "ac", run << 4 | size, z[i]))
+                        run = 0
+                    if run:                                 # coefficient 63 is zero
+                        put(*ac_codes[tq][0x00])
+                        if trace is not None:
+                            trace.append((b, row, blk, "ac", 0x00, 0))
+            if nacc:
+                put((1 << (8 - nacc)) - 1, 8 - nacc)
+            overflow = overflow or len(seg) > seg_cap
+            out += seg
+            out += bytes([0xFF, 0xD0 + row % 8]) if row < my - 1 else b"\xff\xd9"
+        if overflow or len(out) > cap:
+            nbytes[b] = -1
+        else:
+            nbytes[b] = len(out)
+            stream[b, :len(out)] = torch.frombuffer(out, dtype=torch.uint8)
+    return stream, nbytes
