@@ -1,7 +1,9 @@
-"""Plain PyTorch fp32 references of the native ops — used ONLY by tests / numerics checks.
+"""Plain PyTorch references of the native ops — used ONLY by tests / numerics checks.
 
-Every HIP kernel in ``csrc/kernels`` has a counterpart here operating on NCHW fp32 tensors
-(torch's native layout) so the tests compare two independent implementations.
+Every HIP kernel in ``csrc/kernels`` has a counterpart here operating on NCHW tensors (torch's
+native layout) so the tests compare two independent implementations.  ``conv_ref`` and
+``linear_ref`` follow the dtype of their input: fp32, or fp64 for the per-pixel / per-channel
+bounds of the conv tests.
 """
 from __future__ import annotations
 
@@ -22,14 +24,33 @@ def act_ref(x: torch.Tensor, act: int) -> torch.Tensor:
     return x
 
 
+def _conv_taps(x, w, b, stride: int, pad: int) -> torch.Tensor:
+    """The convolution as one matmul per filter tap on strided views of the padded input: the
+    fp64 form for a device, where only matmul is relied on in fp64."""
+    B, _, H, W = x.shape
+    R, S = w.shape[2:]
+    Ho, Wo = (H + 2 * pad - R) // stride + 1, (W + 2 * pad - S) // stride + 1
+    xp = F.pad(x, (pad, pad, pad, pad))
+    y = torch.zeros(B, w.shape[0], Ho, Wo, dtype=x.dtype, device=x.device)
+    for r in range(R):
+        for s in range(S):
+            tap = xp[:, :, r:r + stride * (Ho - 1) + 1:stride, s:s + stride * (Wo - 1) + 1:stride]
+            y += torch.einsum("bchw,oc->bohw", tap, w[:, :, r, s])
+    return y if b is None else y + b.view(1, -1, 1, 1)
+
+
 def conv_ref(x_nchw: torch.Tensor, spec: ConvSpec, residual_nchw: torch.Tensor | None = None,
              residual_after_act: bool = False) -> torch.Tensor:
-    w = spec.ref_weight.to(x_nchw.device)
-    b = None if spec.ref_bias is None else spec.ref_bias.to(x_nchw.device)
-    if spec.kind == "stem":
-        y = F.conv2d(x_nchw, w, b, stride=spec.stride, padding=spec.stem_pad)
+    """In the dtype of ``x_nchw``: fp32 as the tests' plain reference, fp64 (``x.double()``) for
+    the per-pixel / per-channel bounds.  ``ref_weight`` is the bf16-rounded weight, so kernel
+    and reference start from the same operands."""
+    w = spec.ref_weight.to(device=x_nchw.device, dtype=x_nchw.dtype)
+    b = None if spec.ref_bias is None else spec.ref_bias.to(device=x_nchw.device, dtype=x_nchw.dtype)
+    pad = spec.stem_pad if spec.kind == "stem" else spec.pad
+    if x_nchw.dtype == torch.float64 and x_nchw.is_cuda:
+        y = _conv_taps(x_nchw, w, b, spec.stride, pad)
     else:
-        y = F.conv2d(x_nchw, w, b, stride=spec.stride, padding=spec.pad)
+        y = F.conv2d(x_nchw, w, b, stride=spec.stride, padding=pad)
     if residual_nchw is not None and residual_after_act:
         return act_ref(y, spec.act) + residual_nchw
     if residual_nchw is not None:
@@ -38,8 +59,8 @@ def conv_ref(x_nchw: torch.Tensor, spec: ConvSpec, residual_nchw: torch.Tensor |
 
 
 def linear_ref(x: torch.Tensor, spec: ConvSpec) -> torch.Tensor:
-    w = spec.ref_weight.to(x.device).reshape(spec.cout, -1)
-    b = None if spec.ref_bias is None else spec.ref_bias.to(x.device)
+    w = spec.ref_weight.to(device=x.device, dtype=x.dtype).reshape(spec.cout, -1)
+    b = None if spec.ref_bias is None else spec.ref_bias.to(device=x.device, dtype=x.dtype)
     return act_ref(F.linear(x, w, b), spec.act)
 
 

@@ -1,7 +1,8 @@
 """Plain/guarded operand factory, the two-run driver and the error metrics shared by the guard
 test files (tests/test_gpu_guard.py: conv and vision kernels; tests/test_gpu_guard_transformer.py:
-the Whisper path).  A plain module next to ``kernel_guard.py``: no fixtures; ``row_err`` and
-``rel_err`` work on the CPU."""
+the Whisper path).  A plain module next to ``kernel_guard.py``: no fixtures; the metrics
+(``rel_err``, ``row_errs`` / ``row_err``, ``pixel_channel_errs`` / ``assert_pixel_channel``) work
+on the CPU."""
 from __future__ import annotations
 
 import dataclasses
@@ -29,18 +30,65 @@ def rel_err(a, b):
     return ((a - b).norm() / (b.norm() + 1e-12)).item()
 
 
-def row_err(y, ref):
-    """``max_m ||y[m] - ref[m]|| / ||ref[m]||`` over the rows of a 2-D tensor (in fp64).  A row
+def row_errs(y, ref):
+    """``||y[m] - ref[m]|| / ||ref[m]||`` of every row m of a 2-D tensor, an fp64 vector.  A row
     whose reference norm is 0 is compared exactly: any non-zero element there, like any
     non-finite element anywhere, gives ``inf``."""
     y, ref = y.double(), ref.double()
     assert y.dim() == 2 and y.shape == ref.shape, (y.shape, ref.shape)
-    if y.numel() == 0:
-        return 0.0
     num, den = (y - ref).norm(dim=1), ref.norm(dim=1)
     err = torch.where(den > 0, num / den.clamp(min=1e-300), torch.where(num == 0, 0.0, float("inf")))
-    err = torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))
-    return err.max().item()
+    return torch.where(torch.isfinite(err), err, torch.full_like(err, float("inf")))
+
+
+def row_err(y, ref):
+    """``max_m`` of :func:`row_errs` (0 for an empty tensor)."""
+    errs = row_errs(y, ref)
+    return errs.max().item() if errs.numel() else 0.0
+
+
+def pixel_channel_errs(y_nhwc, ref_nhwc):
+    """``(per_pixel[M], per_channel[N])`` of an NHWC (or ``[M, N]``) output: :func:`row_errs` of
+    the ``[M, N]`` view (M = every dimension but the last) and of its transpose."""
+    assert y_nhwc.shape == ref_nhwc.shape, (y_nhwc.shape, ref_nhwc.shape)
+    N = y_nhwc.shape[-1]
+    y, ref = y_nhwc.reshape(-1, N).double(), ref_nhwc.reshape(-1, N).double()
+    if y.device != ref.device:
+        y = y.to(ref.device)
+    return row_errs(y, ref), row_errs(y.T, ref.T)
+
+
+def _where(idx, shape):
+    """Flat pixel index -> ``(b, h, w)`` for an NHWC shape, ``(m,)`` otherwise."""
+    if len(shape) != 4:
+        return (int(idx),)
+    _, H, W, _ = shape
+    return (int(idx) // (H * W), int(idx) // W % H, int(idx) % W)
+
+
+def assert_pixel_channel(y_nhwc, ref_nhwc, bound=ROW_BOUND, what=""):
+    """Print the worst pixel (as ``(b, h, w)`` and flat row) and the worst channel, then assert
+    both are below ``bound``.  The failure message counts the pixels and channels over the bound
+    and names the first and the last of each, so a tile or border pattern shows in the log.
+    Returns ``(worst pixel error, worst channel error)``."""
+    pix, ch = pixel_channel_errs(y_nhwc, ref_nhwc)
+    shape = tuple(y_nhwc.shape)
+    pi, ci = int(pix.argmax()), int(ch.argmax())
+    pe, ce = pix[pi].item(), ch[ci].item()
+    print(f"parity {what}: shape {shape} worst pixel {_where(pi, shape)} (row {pi}) {pe:.3e}, "
+          f"worst channel {ci} {ce:.3e}, bound {bound:.3e}")
+    bad_p, bad_c = torch.nonzero(~(pix < bound)).flatten().tolist(), torch.nonzero(~(ch < bound)).flatten().tolist()
+    if bad_p or bad_c:
+        msg = [f"{what}: per-pixel / per-channel bound {bound:.3e} exceeded (shape {shape})"]
+        if bad_p:
+            msg.append(f"{len(bad_p)} of {pix.numel()} pixels: first {_where(bad_p[0], shape)} (row {bad_p[0]}) "
+                       f"{pix[bad_p[0]].item():.3e}, last {_where(bad_p[-1], shape)} (row {bad_p[-1]}) "
+                       f"{pix[bad_p[-1]].item():.3e}, worst row {pi} {pe:.3e}")
+        if bad_c:
+            msg.append(f"{len(bad_c)} of {ch.numel()} channels: first {bad_c[0]} {ch[bad_c[0]].item():.3e}, "
+                       f"last {bad_c[-1]} {ch[bad_c[-1]].item():.3e}, worst {ci} {ce:.3e}")
+        raise AssertionError("; ".join(msg))
+    return pe, ce
 
 
 def attn_split_plan(B, H, T, cus, pieces, nw=8, work_bytes=None):

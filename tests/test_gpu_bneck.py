@@ -1,7 +1,12 @@
 """Fused stage-1 ResNet bottleneck (bneck_fused.hip) vs a plain PyTorch fp32 reference of the
-same block, and vs the unfused kernel path (conv3x3_patch / conv_chain / igemm)."""
+same block, vs the unfused kernel path (conv3x3_patch / conv_chain / igemm), and — per pixel and
+per channel, bound 2^-8 — vs an fp64 reference that rounds t1 and t2 to bf16 where the kernel
+keeps them as bf16 in LDS (the identity or projection shortcut is added unrounded)."""
 import pytest
 import torch
+
+import conv_parity_cases as P
+from guard_ops import ROW_BOUND, assert_pixel_channel
 
 pytestmark = pytest.mark.gpu
 
@@ -13,19 +18,6 @@ def _rel(a, b):
     return ((a - b).norm() / (b.norm() + 1e-12)).item()
 
 
-def _block(g, cin, dual):
-    from aiko_services_amd.models.resnet50 import _rand_bn, _rand_conv
-    from aiko_services_amd.ops import conv as C
-    c1 = C.make_conv_spec(*C.fold_bn(_rand_conv(g, 64, cin, 1), *_rand_bn(g, 64)), act="relu", device=DEV)
-    c2 = C.make_conv_spec(*C.fold_bn(_rand_conv(g, 64, 64, 3), *_rand_bn(g, 64)), pad=1, act="relu", device=DEV)
-    c3 = C.make_conv_spec(*C.fold_bn(_rand_conv(g, 256, 64, 1), *_rand_bn(g, 256, (0.1, 0.3))), act="relu",
-                          device=DEV)
-    down = None
-    if dual:
-        down = C.make_conv_spec(*C.fold_bn(_rand_conv(g, 256, cin, 1), *_rand_bn(g, 256)), device=DEV)
-    return c1, c2, c3, down
-
-
 def _reference(x_nchw, c1, c2, c3, down):
     from aiko_services_amd.ops import reference as R
     t = R.conv_ref(x_nchw, c1)
@@ -34,22 +26,12 @@ def _reference(x_nchw, c1, c2, c3, down):
     return R.conv_ref(t.to(torch.bfloat16).float(), c3, residual_nchw=idn)
 
 
-@pytest.mark.parametrize("B,H,dual,grid", [
-    (3, 56, False, 0), (2, 56, True, 0),          # default grid: more CUs than rows, one row each
-    (3, 56, False, 7), (2, 56, True, 3),          # ranges of 24 / 37-38 rows crossing image boundaries
-    (9, 56, False, 5), (5, 56, True, 2),          # ranges spanning three or more images
-    (2, 20, False, 1), (2, 20, True, 1),          # one workgroup streaming two images
-    (1, 56, False, 1), (2, 13, False, 4),         # one image / uneven split (26 = 7 + 7 + 6 + 6)
-    (4, 1, False, 1), (3, 2, True, 2),            # images of one / two rows: a boundary every row or two
-    (40, 56, False, 0), (24, 56, True, 0),        # every CU streaming several rows: counted DMA waits
-])
+@pytest.mark.parametrize("B,H,dual,grid", P.BNECK_PARITY_CASES)
 def test_bneck_fused_matches_torch(native, B, H, dual, grid):
     from aiko_services_amd.ops import conv as C
-    g = torch.Generator().manual_seed(B * 1000 + H * 10 + int(dual) + 7 * grid)
-    cin = 64 if dual else 256
-    c1, c2, c3, down = _block(g, cin, dual)
+    pc = P.bneck_case(B, H, dual, grid, DEV)
+    c1, c2, c3, down, x = pc.specs["c1"], pc.specs["c2"], pc.specs["c3"], pc.specs.get("down"), pc.ops["x"]
     conv3 = C.fuse_shortcut(c3, down) if dual else c3
-    x = torch.relu(torch.randn(B, cin, H, 56, generator=g)).to(torch.bfloat16)
     xd = x.permute(0, 2, 3, 1).contiguous().to(DEV)
     out = torch.full((B, H, 56, 256), float("nan"), dtype=torch.bfloat16, device=DEV)
     y = C.bneck_fused(xd, c1, c2, conv3, out=out, grid=grid)
@@ -63,6 +45,7 @@ def test_bneck_fused_matches_torch(native, B, H, dual, grid):
     t2 = C.conv2d(t1, c2)
     y2 = C.conv2d(t2, conv3, x2=xd) if dual else C.conv2d(t2, c3, residual=xd)
     assert _rel(y, y2) < 5e-3
+    assert_pixel_channel(y, pc.ref64[0], ROW_BOUND, f"bneck_fused B{B} H{H} dual{int(dual)} grid{grid}")
 
 
 def test_resnet50_stage1_fused_matches_unfused(native, monkeypatch):

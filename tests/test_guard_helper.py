@@ -3,7 +3,7 @@ one-element change on either side of the interior is reported with its side and 
 import pytest
 import torch
 
-from guard_ops import ROW_BOUND, row_err
+from guard_ops import ROW_BOUND, assert_pixel_channel, pixel_channel_errs, row_err, row_errs
 from kernel_guard import ALIGN, BYTE_NAN, GuardError, guard_elems, guarded
 
 DTYPES = [torch.bfloat16, torch.float32, torch.uint8]
@@ -209,3 +209,83 @@ def test_row_err_flags_what_the_whole_tensor_norm_lets_through():
     nobias[M - 5:] = (ref[M - 5:] - bias).to(torch.bfloat16)
     assert _rel(nobias, ref) < 5e-3
     assert row_err(nobias, ref) > ROW_BOUND
+
+
+# ---- the per-pixel / per-channel metric ------------------------------------------------------------
+
+def _pc_ref():
+    g = torch.Generator().manual_seed(3)
+    return torch.randn(2, 3, 5, 8, generator=g, dtype=torch.float64) + 0.5
+
+
+def test_row_errs_is_what_row_err_reduces():
+    ref = torch.tensor([[3.0, 4.0], [0.0, 0.0], [1.0, 0.0]])
+    y = ref.clone()
+    y[0, 0] = 3.5
+    errs = row_errs(y, ref)
+    assert errs.dtype == torch.float64 and errs.shape == (3,)
+    assert abs(errs[0].item() - 0.1) < 1e-12 and errs[1].item() == 0.0 and errs[2].item() == 0.0
+    assert row_err(y, ref) == errs.max().item()
+    empty = torch.zeros(0, 4)
+    assert row_errs(empty, empty).numel() == 0 and row_err(empty, empty) == 0.0
+
+
+def test_pixel_channel_errs_exact_row_column_zero_norm_and_nan():
+    ref = _pc_ref()
+    pix, ch = pixel_channel_errs(ref.clone(), ref)
+    assert pix.shape == (30,) and ch.shape == (8,) and pix.max().item() == 0.0 and ch.max().item() == 0.0
+    assert_pixel_channel(ref.clone(), ref, ROW_BOUND, "exact")
+    y = ref.clone()
+    y[1, 2, 4] *= 1.01                                                     # one pixel row off by 1 %
+    pix, ch = pixel_channel_errs(y, ref)
+    assert abs(pix[29].item() - 0.01) < 1e-12 and (pix[:29] == 0).all()
+    assert (ch > 0).all() and ch.max().item() < 0.01                       # one of 30 entries per column
+    y = ref.clone()
+    y[..., 5] *= 1.01                                                      # one channel column off by 1 %
+    pix, ch = pixel_channel_errs(y, ref)
+    assert abs(ch[5].item() - 0.01) < 1e-12 and ch[:5].max().item() == 0 and ch[6:].max().item() == 0
+    assert (pix > 0).all() and pix.max().item() < 0.01
+    zref = ref.clone()
+    zref[0, 1, 3] = 0                                                      # a zero-norm pixel row: compared exactly
+    pix, _ = pixel_channel_errs(zref.clone(), zref)
+    assert pix.max().item() == 0.0
+    y = zref.clone()
+    y[0, 1, 3, 2] = 1e-30
+    pix, ch = pixel_channel_errs(y, zref)
+    assert pix[8].item() == float("inf") and torch.isfinite(ch).all()
+    y = ref.clone()
+    y[0, 0, 1, 6] = float("nan")
+    pix, ch = pixel_channel_errs(y, ref)
+    assert pix[1].item() == float("inf") and ch[6].item() == float("inf")
+    assert torch.isfinite(pix).sum().item() == 29 and torch.isfinite(ch).sum().item() == 7
+    pix2, ch2 = pixel_channel_errs(ref.reshape(30, 8).to(torch.bfloat16), ref.reshape(30, 8))   # [M, N], any dtype
+    assert 0 < pix2.max().item() < ROW_BOUND and 0 < ch2.max().item() < ROW_BOUND
+
+
+def test_assert_pixel_channel_names_the_pattern(capsys):
+    ref = _pc_ref()
+    pe, ce = assert_pixel_channel(ref.to(torch.bfloat16), ref, ROW_BOUND, "clean")
+    assert 0 < pe < ROW_BOUND and 0 < ce < ROW_BOUND
+    out = capsys.readouterr().out
+    assert "clean" in out and "worst pixel (" in out and "worst channel" in out
+    y = ref.clone()
+    y[1, 0, 4] *= 1.05                                                     # right-hand column of image 1
+    y[1, 2, 4] *= 1.05
+    with pytest.raises(AssertionError) as e:
+        assert_pixel_channel(y, ref, ROW_BOUND, "border")
+    msg = str(e.value)
+    assert "border" in msg and "2 of 30 pixels" in msg and "first (1, 0, 4) (row 19)" in msg
+    assert "last (1, 2, 4) (row 29)" in msg
+    assert "worst pixel (1," in capsys.readouterr().out                    # printed before it asserts
+    y = ref.clone()
+    y[..., 7] = 0                                                          # the last channel lost
+    with pytest.raises(AssertionError) as e:
+        assert_pixel_channel(y, ref, ROW_BOUND, "tail")
+    assert "1 of 8 channels: first 7" in str(e.value) and "last 7" in str(e.value)
+    y = ref.clone()
+    y[0, 0, 0, 0] = float("nan")
+    with pytest.raises(AssertionError) as e:
+        assert_pixel_channel(y, ref, ROW_BOUND, "nan")
+    assert "1 of 30 pixels" in str(e.value) and "1 of 8 channels" in str(e.value) and "inf" in str(e.value)
+    with pytest.raises(AssertionError):
+        assert_pixel_channel(ref.clone(), ref, 0.0, "zero bound")          # strictly below the bound
