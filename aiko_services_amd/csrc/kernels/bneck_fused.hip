@@ -55,6 +55,18 @@
 // N = the wave's VMEM ops issued after the awaited DMA (the previous row's y stores and the next
 // row's DMAs — the stores are inline asm too, so the count is exact and the compiler inserts no
 // vmcnt(0) drains of its own).
+//
+// Two instances per CIN under one name, bneck_fused_kernel<CIN, LEAN>, bit-identical in output:
+//   * LEAN = false, the experiment kernel described above: one flat row loop over virtual rows,
+//     the schedule / ablation bits of AIKO_BN_MODE tested at run time, per-row s_memtime stamps,
+//     and a mark word + a switch to turn each run-time DMA count into an immediate s_waitcnt;
+//   * LEAN = true, the production instance (launched for the default mode 1024 without stamps,
+//     unless AIKO_BN_LEAN=0): the shipped schedule only.  It treats the x rows of a range as the
+//     contiguous flat rows they are in memory (halo rows exist only as zero t1 rows), nests the
+//     rows by image (general rows at the segment ends, a test-free interior row), rotates ring
+//     slots as scalars and waits with derived immediates: vmcnt(ST + dw) while the DMA stream
+//     runs, vmcnt(ST) after it ends (derivation at the loop).  Per wave and output row that is 43
+//     scalar ALU instructions against 224 (identity block, PMC: profiles/bneck_lean.md).
 #include <cstdlib>
 #include <type_traits>
 
@@ -128,6 +140,25 @@ __device__ __forceinline__ void bn_store16(bf16_t* p, u32x4 v) {
   asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
 }
 
+// the lean instance's forms: a wave-uniform row pointer + a per-lane byte offset that never
+// changes.  The address is still a 64-bit per-lane VGPR pair: the scalar-base form of the same
+// instructions (row in SGPRs, a 32-bit lane offset) measured within the round-to-round spread of
+// this one and was dropped (profiles/bneck_lean.md, step 5).  The store keeps the wait states of
+// bn_store16; HALF is the +32-channel (64-byte) half of the lane's pixel
+template <bool HALF>
+__device__ __forceinline__ void bn_store16_row(const unsigned char* row, uint32_t off, u32x4 v) {
+  if constexpr (HALF)
+    asm volatile("global_store_dwordx4 %0, %1, off offset:64\n\ts_nop 1" :: "v"(row + off), "v"(v) : "memory");
+  else
+    asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" :: "v"(row + off), "v"(v) : "memory");
+}
+
+// glds16_asm (common.h) with the LDS destination already a scalar: m0 + lane * 16
+__device__ __forceinline__ void bn_glds16_row(const unsigned char* row, uint32_t off, uint32_t m0v) {
+  asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off"
+               :: "v"(row + off), "s"(m0v) : "memory", "m0");
+}
+
 template <int OFF>
 __device__ __forceinline__ bf16x8 bn_ld(const unsigned char* base) {
   return *reinterpret_cast<const bf16x8*>(base + OFF);
@@ -140,7 +171,9 @@ __device__ __forceinline__ uint32_t bn_relu2(uint32_t v) {
   return __builtin_bit_cast(uint32_t, r);
 }
 
-template <int CIN>
+// LEAN = false: the experiment kernel, with the run-time schedule / ablation bits of p.mode and the
+// per-row stamps.  LEAN = true: the production instance, the shipped schedule only (see the header)
+template <int CIN, bool LEAN>
 __global__ __launch_bounds__(64 * kBnNW, 1) void bneck_fused_kernel(BnParams p) {
   constexpr bool DUAL = CIN == 64;                 // projection block (stage-1 entry)
   constexpr int NC = CIN / 8;                      // 16-byte channel chunks per pixel
@@ -396,6 +429,231 @@ __global__ __launch_bounds__(64 * kBnNW, 1) void bneck_fused_kernel(BnParams p) 
     ops += ST;
   };
 
+  if constexpr (LEAN) {
+    // ---- the production row loop: the default schedule only (conv2 split at the end of phase B,
+    // conv1 before conv3), no p.mode, no stamps, the same products in the same order as the generic
+    // loop below, so the output is bit-identical.  What differs is the bookkeeping:
+    //   * the x rows a range needs are CONTIGUOUS in global memory — flat rows F0 .. F1 of
+    //     [B * H], image boundaries included; the halo rows are not x rows at all.  So the DMA
+    //     stream is one pointer that advances by XROWG per output row, and the x ring holds four
+    //     consecutive flat rows: at output row f the slots X[0 .. 3] hold f (conv3's residual),
+    //     f + 1, f + 2 (waited for in phase A, conv1's input in phase B while it is in f's image)
+    //     and f + 3 (issued at the top of f into the slot of f - 1, which conv3 last read before
+    //     the previous row's closing barrier).  Across an image boundary the next image's first
+    //     rows arrive during the last rows of this one;
+    //   * ring slots rotate as scalars (X[], T[]); the halo shows only in the t1 ring: rows H and
+    //     H + 1 (= row -1 of the next image) are written as zeros, and at the boundary the t1
+    //     slots do NOT rotate (the generic loop's v += 3 is the identity on v % 3);
+    //   * rows are nested by image: a general row (the segment's first row, and its last ones:
+    //     boundary phase, zero rows, no split, end of the DMA stream) and an interior row with no
+    //     tests at all;
+    //   * every DMA wait is an immediate.  Wave-uniform VMEM issue order per output row f:
+    //       [dw DMAs of row f + 3]  ...  wait(f + 2)  ...  [ST stores of y row f]
+    //     Row f + 2 was issued at the top of row f - 1, so between its DMAs and its wait the wave
+    //     issued the ST stores of row f - 1 and the dw DMAs of row f + 3: vmcnt(ST + dw), dw = DQ or
+    //     DQ - 1 by wave.  Once the stream has ended (f + 3 > F1) only the stores follow it:
+    //     vmcnt(ST).  Rows up to R0 + 2 are issued and drained (vmcnt(0)) by the prologue, so in
+    //     the range's first rows the same waits are merely early.  Every wave waits for its own
+    //     DMAs of a row before a barrier that every reader of the row passes later: conv1 of
+    //     f + 2 in this phase B, or (rows 0 and 1 of an image) the boundary phase one or two rows
+    //     later, and conv3 at row f + 2.
+    static_assert(ST + DQ <= 28, "bn_vm_wait");
+    const int Rend = R0 + nrows;                       // flat output rows [R0, Rend)
+    const int nle = (Rend - 1) / H, hle = Rend - 1 - nle * H;
+    const int F0 = h0 > 0 ? R0 - 1 : R0;               // first and last flat x row the range reads
+    const int F1 = hle + 1 < H ? Rend : Rend - 1;
+    const unsigned char* const xg = reinterpret_cast<const unsigned char*>(p.x);
+    const uint32_t xm0 = __builtin_amdgcn_readfirstlane(static_cast<uint32_t>(reinterpret_cast<uintptr_t>(xr))) +
+                         wv * 1024;
+    auto dma_row = [&](const unsigned char* src, uint32_t slot) {    // one x row -> ring slot (bytes)
+#pragma unroll
+      for (int q = 0; q < DQ; ++q)
+        if (gok[q]) bn_glds16_row(src, (uint32_t)goff[q], xm0 + slot + q * (kBnNW * 1024));
+    };
+    auto wait_dma = [&]() {
+      if (dw == DQ) bn_vm_wait(ST + DQ);
+      else bn_vm_wait(ST + DQ - 1);
+    };
+    // conv1 of the x row in ring slot xo -> t1 slot to (byte offsets); a zero row for the halo
+    auto conv1_x = [&](uint32_t xo, uint32_t to) {
+      unsigned char* t1w = t1r + to + twb;
+      const unsigned char* xs = xr + xo + xlb;
+      f32x4 a1[kBnTPW];
+#pragma unroll
+      for (int ks = 0; ks < KS1; ++ks) {
+        bf16x8 bf[kBnTPW];
+#pragma unroll
+        for (int t = 0; t < kBnTPW; ++t)
+          bf[t] = *reinterpret_cast<const bf16x8*>(xs + (16 * t * XPU + 4 * ks) * 16);
+#pragma unroll
+        for (int t = 0; t < kBnTPW; ++t)
+          a1[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f[ks], bf[t], ks == 0 ? bias1 : a1[t], 0, 0, 0);
+      }
+      bn_pipeline<KS1, kBnTPW, KS1 >= 4 ? 3 : 1>();
+#pragma unroll
+      for (int t = 0; t < kBnTPW; ++t) {
+        uint2 pk{bn_relu2(pack2(a1[t][0], a1[t][1])), bn_relu2(pack2(a1[t][2], a1[t][3]))};
+        if (pt0 + t == 3 && fr >= kBnW - 48) pk = uint2{0u, 0u};   // pixel slots 56..63: zero pad
+        *reinterpret_cast<uint2*>(t1w + (1 + 16 * t) * 16) = pk;
+      }
+    };
+    auto conv1_zero = [&](uint32_t to) {
+      unsigned char* t1w = t1r + to + twb;
+#pragma unroll
+      for (int t = 0; t < kBnTPW; ++t) *reinterpret_cast<uint2*>(t1w + (1 + 16 * t) * 16) = uint2{0u, 0u};
+    };
+    // conv2 k-steps [KB, KE) of the output row whose t1 rows above / at / below sit in slots o0 / o1 / o2
+    auto conv2_rows = [&](uint32_t o0, uint32_t o1, uint32_t o2, auto kb, auto ke) __attribute__((always_inline)) {
+      constexpr int KB = decltype(kb)::value, KE = decltype(ke)::value;
+      const unsigned char* tr[3] = {t1r + o0 + tlb, t1r + o1 + tlb, t1r + o2 + tlb};
+#pragma unroll
+      for (int ks = KB; ks < KE; ++ks) {
+        const int tap = ks >> 1, dy = tap / 3, dx = tap % 3 - 1, hk = ks & 1;
+        bf16x8 bf[kBnTPW];
+#pragma unroll
+        for (int t = 0; t < kBnTPW; ++t)
+          bf[t] = *reinterpret_cast<const bf16x8*>(tr[dy] + (1 + 256 * hk + 16 * t + dx) * 16);
+#pragma unroll
+        for (int t = 0; t < kBnTPW; ++t)
+          a2n[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f[ks], bf[t], ks == 0 ? bias2 : a2n[t], 0, 0, 0);
+      }
+      bn_pipeline<KE - KB, kBnTPW, 4>();
+    };
+    // conv3 (+ residual / projection of the x row in ring slot xo) -> the y row at yrow
+    const uint32_t yoff = ((16 * pt0 + fr) * kBnOut + 64 * cg + 8 * fq) * 2;
+    auto conv3_row = [&](uint32_t xo, const unsigned char* yrow) {
+      const unsigned char* xres = xr + xo + xlb;
+      const unsigned char* t2r = t2b + tlb;
+#pragma unroll
+      for (int t8 = 0; t8 < kBnTPW; ++t8) {
+        bf16x8 bf[KS3];
+#pragma unroll
+        for (int ks = 0; ks < KS3; ++ks)
+          bf[ks] = ks < 2 ? *reinterpret_cast<const bf16x8*>(t2r + (1 + 256 * ks + 16 * t8) * 16)
+                          : *reinterpret_cast<const bf16x8*>(xres + (16 * t8 * XPU + 4 * (ks - 2)) * 16);
+        bf16x8 rv[2];
+        if constexpr (!DUAL) {
+#pragma unroll
+          for (int h = 0; h < 2; ++h)
+            rv[h] = *reinterpret_cast<const bf16x8*>(xres + (16 * t8 * XPU + 8 * cg + 4 * h) * 16);
+        }
+        f32x4 a3[4];
+#pragma unroll
+        for (int ks = 0; ks < KS3; ++ks)
+#pragma unroll
+          for (int t = 0; t < 4; ++t)
+            a3[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w3f[t][ks], bf[ks], ks == 0 ? bias3[t] : a3[t], 0, 0, 0);
+        if constexpr (!DUAL) {
+#pragma unroll
+          for (int t = 0; t < 4; ++t) a3[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(eye[t & 1], rv[t >> 1], a3[t], 0, 0, 0);
+        }
+        const uint32_t yo = yoff + t8 * (16 * kBnOut * 2);
+        const bool live = 16 * (pt0 + t8) + fr < kBnW;
+        const u32x4 o0{bn_relu2(pack2(a3[0][0], a3[0][1])), bn_relu2(pack2(a3[0][2], a3[0][3])),
+                       bn_relu2(pack2(a3[1][0], a3[1][1])), bn_relu2(pack2(a3[1][2], a3[1][3]))};
+        if (live) bn_store16_row<false>(yrow, yo, o0);
+        const u32x4 o1{bn_relu2(pack2(a3[2][0], a3[2][1])), bn_relu2(pack2(a3[2][2], a3[2][3])),
+                       bn_relu2(pack2(a3[3][0], a3[3][1])), bn_relu2(pack2(a3[3][2], a3[3][3]))};
+        if (live) bn_store16_row<true>(yrow, yo, o1);
+      }
+    };
+
+    // ring state, all wave-uniform scalars
+    const uint32_t s0 = h0 > 0 ? 1u : 0u;              // flat row F0 + s is DMA'd into slot s & 3
+    uint32_t X0 = s0 * XB, X1 = (s0 + 1) * XB, X2 = (s0 + 2) * XB, X3 = ((s0 + 3) & 3u) * XB;
+    uint32_t T0 = 0, T1 = kBnTB, T2 = 2 * kBnTB;       // t1 slots of rows r - 1, r, r + 1
+    int f = R0;                                        // the flat output row
+    const unsigned char* src = xg + (long)(R0 + 3) * XROWG;                       // x row f + 3
+    const unsigned char* yp = reinterpret_cast<const unsigned char*>(p.y) + (long)R0 * (kBnW * kBnOut * 2);
+    bool pre = false;                                  // a2n holds this row's first 12 conv2 k-steps
+    auto advance = [&]() {
+      ++f;
+      src += XROWG;
+      yp += kBnW * kBnOut * 2;
+      const uint32_t x0 = X0;
+      X0 = X1, X1 = X2, X2 = X3, X3 = x0;
+    };
+    auto rotate_t1 = [&]() {
+      const uint32_t t0 = T0;
+      T0 = T1, T1 = T2, T2 = t0;
+    };
+
+    // row r of an image whose segment ends at rb (exclusive) and whose last real t1 row is xe
+    auto row_general = [&](int r, int rb, int xe, bool boundary) {
+      const bool dma = f + 3 <= F1;
+      if (dma) dma_row(src, X3);
+      if (boundary) {                                  // a new image: t1 rows 0 and 1 first (row -1 is
+        conv1_x(X0, T1);                               // the zero row the last image's row H - 1 left)
+        if (1 <= xe) conv1_x(X1, T2);
+        else conv1_zero(T2);
+        bn_barrier();
+      }
+      if (pre) conv2_rows(T0, T1, T2, KBS{}, KBE{});
+      else conv2_rows(T0, T1, T2, KB0{}, KBE{});
+      conv2_store();
+      if (dma) wait_dma();
+      else bn_vm_wait(ST);
+      bn_barrier();
+      if (r + 2 <= xe) conv1_x(X2, T0);
+      else conv1_zero(T0);
+      conv3_row(X0, yp);
+      pre = r + 1 < rb;
+      if (pre) {
+        rotate_t1();
+        conv2_rows(T0, T1, T2, KB0{}, KBS{});
+      }
+      bn_barrier();
+      advance();
+    };
+    // an interior row: the DMA stream runs, rows r + 1 .. r + 3 are real rows of the same image
+    auto row_interior = [&]() {
+      dma_row(src, X3);
+      conv2_rows(T0, T1, T2, KBS{}, KBE{});
+      conv2_store();
+      wait_dma();
+      bn_barrier();
+      conv1_x(X2, T0);
+      conv3_row(X0, yp);
+      rotate_t1();
+      conv2_rows(T0, T1, T2, KB0{}, KBS{});
+      bn_barrier();
+      advance();
+    };
+
+    int r = h0, rem = nrows;
+    {                                                  // range prologue: x rows F0 .. R0 + 2, t1 rows h0 - 1 .. h0 + 1
+      const unsigned char* s = xg + (long)F0 * XROWG;
+      const int npro = min(R0 + 2, F1) - F0 + 1;
+      for (int k = 0; k < npro; ++k, s += XROWG) dma_row(s, k * XB);
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      bn_barrier();
+      if (h0 > 0) conv1_x(X3, T0);
+      else conv1_zero(T0);
+      conv1_x(X0, T1);
+      if (h0 + 1 <= min(min(H, h0 + nrows), H - 1)) conv1_x(X1, T2);
+      else conv1_zero(T2);
+      bn_barrier();
+    }
+    bool boundary = false;                             // the range's first row: the prologue did it
+    while (rem > 0) {                                  // one image segment per pass: rows [r, rb)
+      const int rb = min(H, r + rem);
+      const int xe = min(rb, H - 1);
+      // interior rows: r + 2 <= xe, and r + 3 <= xe where the DMA stream ends in this image
+      const int rint = r + rem <= H ? xe - 2 : xe - 1;
+      rem -= rb - r;
+      for (;;) {
+        row_general(r, rb, xe, boundary);
+        boundary = false;
+        if (++r >= rb) break;
+        for (; r < rint; ++r) row_interior();          // rint < rb: a general row follows
+      }
+      r = 0;
+      boundary = true;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    return;
+  }
+
   // ---- prologue: virtual rows h0 .. h0 + 3 in flight, t1 rows of h0 .. h0 + 2 (the first
   //      output row is centred on vc = h0 + 1)
   while (vdma <= min(h0 + 3, vlast)) dma_next();
@@ -526,9 +784,12 @@ extern "C" int aiko_bneck_fused(const void* x, const void* w1, const float* b1, 
   // counted waits worked (round 6: 544 vs 561 us identity, 475 vs 486 us projection at B=640)
   const char* mode = getenv("AIKO_BN_MODE");
   p.mode = mode ? atoi(mode) : 1024;
-  if (cin == 256)
-    hipLaunchKernelGGL(bneck_fused_kernel<256>, dim3(G), dim3(64 * kBnNW), 0, stream, p);
-  else
-    hipLaunchKernelGGL(bneck_fused_kernel<64>, dim3(G), dim3(64 * kBnNW), 0, stream, p);
+  // the lean instance is that default schedule and nothing else: every other mode, a stamp run
+  // and AIKO_BN_LEAN=0 (the A/B against it) take the generic instance
+  const char* lean = getenv("AIKO_BN_LEAN");
+  const bool use_lean = dbg == nullptr && p.mode == 1024 && !(lean && atoi(lean) == 0);
+  auto* kernel = cin == 256 ? (use_lean ? bneck_fused_kernel<256, true> : bneck_fused_kernel<256, false>)
+                            : (use_lean ? bneck_fused_kernel<64, true> : bneck_fused_kernel<64, false>);
+  hipLaunchKernelGGL(kernel, dim3(G), dim3(64 * kBnNW), 0, stream, p);
   return (int)hipGetLastError();
 }
