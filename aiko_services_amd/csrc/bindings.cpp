@@ -14,37 +14,23 @@
 #include <cmath>
 #include <vector>
 
+#include "kernels/conv_launch.h"
+
 extern "C" {
-int aiko_conv_igemm(const void* x, const void* w, const float* bias, const void* res, void* y,
-                    int H, int W, int C, int Cc, int R, int S, int stride, int pad, int Ho,
-                    int Wo, int M, int Cout, int K, int act, int ldy, int ldr, int bm, int bn,
-                    const void* x2, int K1, int H2, int W2, int C2, int stride2, hipStream_t stream);
-int aiko_conv_buf(const void* x, const void* w, const float* bias, const void* res, void* y,
-                  int H, int W, int C, int Cc, int R, int S, int stride, int pad, int Ho, int Wo,
-                  int M, int Cout, int K, int act, int ldy, int ldr, int bm, int bn, const void* x2,
-                  int K1, int H2, int W2, int C2, int stride2, int occ, int mf32, hipStream_t stream);
-int aiko_conv_wide(const void* x, const void* w, const float* bias, const void* res, void* y,
-                   int H, int W, int C, int Cc, int R, int S, int stride, int pad, int Ho, int Wo,
-                   int M, int Cout, int K, int act, int ldy, int ldr, int bm, int bn, const void* x2,
-                   int K1, int H2, int W2, int C2, int stride2, int occ, hipStream_t stream);
+int aiko_conv_igemm(const ConvLaunch* l);
+int aiko_conv_glds(const ConvLaunch* l, const void* zero);
+int aiko_conv_buf(const ConvLaunch* l, int occ, int mf32);
+int aiko_conv_persist(const ConvLaunch* l);
+int aiko_conv_wide(const ConvLaunch* l, int occ);
 int aiko_conv_pw(const void* x, const void* w, const float* bias, const void* res, void* y, int M, int N,
                  int K, int ldx, int ldy, int ldr, int act, int cus, int mode, hipStream_t stream);
 int aiko_conv_pw_dual(const void* x, const void* x2, const void* w, const float* bias, void* y, int M, int N,
                       int ldx, int ldx2, int ldy, int act, int Ho, int Wo, int H2, int W2, int s2, int cus,
                       hipStream_t stream);
-int aiko_conv_persist(const void* x, const void* w, const float* bias, const void* res, void* y,
-                      int H, int W, int C, int Cc, int R, int S, int stride, int pad, int Ho, int Wo,
-                      int M, int Cout, int K, int act, int ldy, int ldr, int bm, int bn, const void* x2,
-                      int K1, int H2, int W2, int C2, int stride2, hipStream_t stream);
 int aiko_conv_glds_tail(const void* x, const void* w, const float* bias, int H, int W, int C, int Cc, int R, int S,
                         int stride, int pad, int Ho, int Wo, int M, int K, int N, int act, const void* w2, const float* b2,
                         void* y2, int ldy2, int ldw2, int act2, const void* zero, const int* dec, void* boxes,
                         float* scores, int* cls, hipStream_t stream);
-int aiko_conv_glds(const void* x, const void* w, const float* bias, const void* res, void* y,
-                   int H, int W, int C, int Cc, int R, int S, int stride, int pad, int Ho,
-                   int Wo, int M, int Cout, int K, int act, int ldy, int ldr, int bm, int bn,
-                   const void* x2, int K1, int H2, int W2, int C2, int stride2, const void* zero,
-                   hipStream_t stream);
 int aiko_preprocess(const void* in, void* out, int B, int Hin, int Win, int Ho, int Wo, int Hp,
                     int Wp, int pad_t, int pad_l, int Hc, int Wc, int off_t, int off_l, float fill,
                     const float* mean, const float* std, int bgr, hipStream_t stream);
@@ -172,13 +158,9 @@ void check_launch(int rc, const char* what) {
 
 // geom = [H, W, C, Cc, R, S, stride, pad, Ho, Wo, M, act, ldy, ldr, bm, bn,
 //         K1, H2, W2, C2, stride2 (the optional second source x2), [variant]]
-// variant 0: register-staged kernel (conv_igemm.hip); 1: LDS-DMA kernel (conv_glds.hip), which
-// needs ``zero`` (>= 16 B of zeros on the device) as the source of conv padding; 2: buffer
-// LDS-DMA kernel (conv_buf.hip, padding by out-of-range buffer reads); 3 / 5 / 6: conv_buf at high
-// occupancy / on 32x32x16 MFMA / as 4-wave wide tiles; 4: persistent conv_buf; 7: direct 3x3 kernel
-// for narrow layers (conv_narrow.hip); 8: 8-wave wide tiles with a register-direct epilogue
-// (conv_wide.hip); 9: the same kernel at several workgroups per CU; 18: conv_wide with exact-N
-// tiles (BN = 80 or 144 channels computed per tile).
+// variant: a ConvVariant (kernels/conv_launch.h; the table with every kernel's tiles is VARIANTS
+// in ops/conv.py), 0 when absent.  CONV_GLDS needs ``zero`` (>= 16 B of zeros on the device) as
+// the source of conv padding.  An id without a case below is an error.
 void conv_igemm_out(const at::Tensor& x, const c10::optional<at::Tensor>& x2, const at::Tensor& w,
                     const c10::optional<at::Tensor>& bias, const c10::optional<at::Tensor>& res,
                     at::Tensor& y, at::IntArrayRef geom, const c10::optional<at::Tensor>& zero) {
@@ -242,93 +224,109 @@ void conv_igemm_out(const at::Tensor& x, const c10::optional<at::Tensor>& x2, co
     TORCH_CHECK(ldr % 8 == 0 && avail_elems(*res) >= (M - 1) * ldr + Cout, "aiko.conv_igemm_out: bad residual");
     rptr = res->data_ptr();
   }
-  int rc;
-  if (variant == 7) {
-    // direct 3x3 kernel for narrow layers (conv_narrow.hip): Cc, Cout in {16, 32}, pad 1, stride 1/2
-    TORCH_CHECK(!dual && ((R == 3 && S == 3 && pad == 1 && (stride == 1 || stride == 2)) ||
-                          (R == 1 && S == 1 && pad == 0 && stride == 1)) &&
-                    (Cc == 16 || Cc == 32) && (Cout == 16 || Cout == 32),
-                "aiko.conv_igemm_out: variant 7 needs a 3x3 / pad 1 / stride 1-2 or 1x1 / stride 1 conv with Cc, Cout in {16, 32}");
-    rc = aiko_conv_narrow(x.data_ptr(), w.data_ptr(), bptr, rptr, y.data_ptr(), H, W, C, Cc, R, S, stride, pad, Ho,
-                          Wo, M, Cout, K, act, ldy, ldr, bm == 16 ? 16 : 8, bn == 64 ? 1 : 0, cur_stream());
-  } else if (variant == 8 || variant == 9 || variant == 11 || variant == 18 || variant == 19 || variant == 20) {
-    // 8-wave wide tiles, transposed product, register-direct epilogue (conv_wide.hip)
-    TORCH_CHECK(Cc % 64 == 0 && R * S <= 32 && x_extent * 2 < (1LL << 31) - 64 && w.numel() * 2 < (1LL << 31),
-                "aiko.conv_igemm_out: variant 8 needs Cc % 64 == 0, R*S <= 32 and operands < 2 GiB");
-    TORCH_CHECK(!dual || avail_elems(*x2) * 2 < (1LL << 31) - 64, "aiko.conv_igemm_out: x2 too large for variant 8");
-    TORCH_CHECK(ldy % 8 == 0 && (!rptr || (ldr % 8 == 0 && reinterpret_cast<uintptr_t>(rptr) % 16 == 0)),
-                "aiko.conv_igemm_out: variant 8 needs 16-B aligned rows");
-    rc = aiko_conv_wide(x.data_ptr(), w.data_ptr(), bptr, rptr, y.data_ptr(), H, W, C, Cc, R, S, stride,
-                        pad, Ho, Wo, M, Cout, K, act, ldy, ldr, bm, bn, x2ptr, K1, H2, W2, C2, stride2,
-                        variant == 18 ? 18 : variant == 19 ? 19 : variant == 20 ? 20 : variant == 11 ? 11 : (variant == 9 ? 2 : 1), cur_stream());
-  } else if (variant == 13 && dual) {
-    // fused projection on the resident-weight pointwise kernel (conv_pw.hip): 1x1 main source of
-    // 128 channels + a 1x1 / stride-s2 second source of 256 channels
-    TORCH_CHECK(R == 1 && S == 1 && stride == 1 && pad == 0 && Cc == 128 && K1 == 128 && K == 384 &&
-                    Cout % 128 == 0 && C % 8 == 0 && !rptr && x_extent * 2 < (1LL << 31) - 64 &&
-                    avail_elems(*x2) * 2 < (1LL << 31) - 64 && avail_elems(y) * 2 < (1LL << 31) && ldy % 8 == 0,
-                "aiko.conv_igemm_out: variant 13 with a second source needs a 128 + 256 column 1x1 projection, "
-                "Cout % 128 == 0, no residual and operands < 2 GiB");
-    TORCH_CHECK(!bptr || reinterpret_cast<uintptr_t>(bptr) % 16 == 0, "aiko.conv_igemm_out: bias alignment");
-    int dev = 0, cus = 0;
-    (void)hipGetDevice(&dev);
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    rc = aiko_conv_pw_dual(x.data_ptr(), x2ptr, w.data_ptr(), bptr, y.data_ptr(), M, Cout, C, C2, ldy, act, Ho, Wo,
-                           H2, W2, stride2, cus, cur_stream());
-  } else if (variant == 12 || variant == 13 || variant == 14) {
-    // persistent pointwise GEMM (conv_pw.hip): 1x1 / stride 1 / one source, K % 256 == 0,
-    // Cout % 128 == 0, x rows = pixels at pitch C
-    const bool pw_shape = variant == 12 ? (K % 256 == 0 && Cout % 128 == 0)
-                                        : ((K == 128 && Cout % 256 == 0) || (K == 256 && Cout % 128 == 0) ||
-                                           (K == 512 && Cout % 64 == 0));
-    TORCH_CHECK(!dual && R == 1 && S == 1 && stride == 1 && pad == 0 && Cc == K && pw_shape &&
-                    C % 8 == 0 && x_extent * 2 < (1LL << 31) - 64 && w.numel() * 2 < (1LL << 31) &&
-                    avail_elems(y) * 2 < (1LL << 31),
-                "aiko.conv_igemm_out: variants 12/13 need a 1x1/s1 single-source conv with K % 256 == 0 "
-                "(13: K = 128 / 256 / 512), Cout a multiple of the channel block and operands < 2 GiB");
-    TORCH_CHECK(ldy % 8 == 0 && (!rptr || (ldr % 8 == 0 && reinterpret_cast<uintptr_t>(rptr) % 16 == 0 &&
-                                          avail_elems(*res) * 2 < (1LL << 31) - 64)),
-                "aiko.conv_igemm_out: variant 12 needs 16-B aligned rows");
-    TORCH_CHECK(!bptr || reinterpret_cast<uintptr_t>(bptr) % 16 == 0, "aiko.conv_igemm_out: bias alignment");
-    static int cus = 0;
-    if (cus == 0) {
-      int dev = 0, n = 0;
-      (void)hipGetDevice(&dev);
-      if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-      cus = n;
+  ConvLaunch L;
+  L.x = x.data_ptr(); L.w = w.data_ptr(); L.bias = bptr; L.res = rptr; L.y = y.data_ptr();
+  L.H = H; L.W = W; L.C = C; L.Cc = Cc; L.R = R; L.S = S; L.stride = stride; L.pad = pad;
+  L.Ho = Ho; L.Wo = Wo; L.M = M; L.Cout = Cout; L.K = K; L.act = act; L.ldy = ldy; L.ldr = ldr;
+  L.bm = bm; L.bn = bn;
+  L.x2 = x2ptr; L.K1 = K1; L.H2 = H2; L.W2 = W2; L.C2 = C2; L.stride2 = stride2;
+  L.stream = cur_stream();
+  // 64-channel K blocks inside one tap, byte offsets in 31 bits (the buffer-DMA kernels)
+  const bool buf_shape = Cc % 64 == 0 && R * S <= 32 && x_extent * 2 < (1LL << 31) - 64 && w.numel() * 2 < (1LL << 31);
+  const bool x2_fits = !dual || avail_elems(*x2) * 2 < (1LL << 31) - 64;
+  int rc = -1;
+  switch (variant) {
+    case CONV_IGEMM:
+      rc = aiko_conv_igemm(&L);
+      break;
+    case CONV_GLDS:
+      TORCH_CHECK(zero.has_value() && zero->defined() && zero->is_cuda() && zero->nbytes() >= 16 &&
+                      reinterpret_cast<uintptr_t>(zero->data_ptr()) % 16 == 0,
+                  "aiko.conv_igemm_out: the LDS-DMA variant needs a zero page tensor (>= 16 B)");
+      rc = aiko_conv_glds(&L, zero->data_ptr());
+      break;
+    case CONV_BUF:
+    case CONV_BUF_OCC:
+    case CONV_BUF_MF32:
+    case CONV_BUF_WIDE4: {
+      TORCH_CHECK(buf_shape, "aiko.conv_igemm_out: variant 2 needs Cc % 64 == 0, R*S <= 32 and operands < 2 GiB");
+      TORCH_CHECK(x2_fits, "aiko.conv_igemm_out: x2 too large for variant 2");
+      // occ: workgroups per CU forced by CONV_BUF_OCC (64x64: 5, else 3); 1 = the 4-wave wide tiles
+      const int occ = variant == CONV_BUF_OCC ? (bm == 64 && bn == 64 ? 5 : 3) : variant == CONV_BUF_WIDE4 ? 1 : 0;
+      rc = aiko_conv_buf(&L, occ, /*mf32=*/variant == CONV_BUF_MF32);
+      break;
     }
-    rc = aiko_conv_pw(x.data_ptr(), w.data_ptr(), bptr, rptr, y.data_ptr(), M, Cout, K, C, ldy, ldr, act, cus,
-                      variant == 13 ? 1 : variant == 14 ? 2 : 0, cur_stream());
-  } else if (variant == 4) {
-    // persistent buffer-LDS-DMA kernel: one K-block stream across each workgroup's run of tiles
-    TORCH_CHECK(Cc % 64 == 0 && R * S <= 32 && K % 64 == 0 && x_extent * 2 < (1LL << 31) - 64 &&
-                    w.numel() * 2 < (1LL << 31),
-                "aiko.conv_igemm_out: variant 4 needs Cc % 64 == 0, R*S <= 32 and operands < 2 GiB");
-    TORCH_CHECK(!dual || avail_elems(*x2) * 2 < (1LL << 31) - 64, "aiko.conv_igemm_out: x2 too large for variant 4");
-    rc = aiko_conv_persist(x.data_ptr(), w.data_ptr(), bptr, rptr, y.data_ptr(), H, W, C, Cc, R, S, stride,
-                           pad, Ho, Wo, M, Cout, K, act, ldy, ldr, bm, bn, x2ptr, K1, H2, W2, C2, stride2,
-                           cur_stream());
-  } else if (variant == 2 || variant == 3 || variant == 5 || variant == 6) {
-    // buffer-LDS-DMA kernel: 64-channel K blocks inside one tap, byte offsets in 31 bits;
-    // variant 3 = the same kernel at forced high occupancy (64x64: 5, 64x128 / 128x64: 3 WG/CU)
-    TORCH_CHECK(Cc % 64 == 0 && R * S <= 32 && x_extent * 2 < (1LL << 31) - 64 && w.numel() * 2 < (1LL << 31),
-                "aiko.conv_igemm_out: variant 2 needs Cc % 64 == 0, R*S <= 32 and operands < 2 GiB");
-    TORCH_CHECK(!dual || avail_elems(*x2) * 2 < (1LL << 31) - 64, "aiko.conv_igemm_out: x2 too large for variant 2");
-    rc = aiko_conv_buf(x.data_ptr(), w.data_ptr(), bptr, rptr, y.data_ptr(), H, W, C, Cc, R, S, stride,
-                       pad, Ho, Wo, M, Cout, K, act, ldy, ldr, bm, bn, x2ptr, K1, H2, W2, C2, stride2,
-                       variant == 3 ? (bm == 64 && bn == 64 ? 5 : 3) : (variant == 6 ? 1 : 0), variant == 5 ? 1 : 0,
-                       cur_stream());
-  } else if (variant == 1) {
-    TORCH_CHECK(zero.has_value() && zero->defined() && zero->is_cuda() && zero->nbytes() >= 16 &&
-                    reinterpret_cast<uintptr_t>(zero->data_ptr()) % 16 == 0,
-                "aiko.conv_igemm_out: the LDS-DMA variant needs a zero page tensor (>= 16 B)");
-    rc = aiko_conv_glds(x.data_ptr(), w.data_ptr(), bptr, rptr, y.data_ptr(), H, W, C, Cc, R, S, stride,
-                        pad, Ho, Wo, M, Cout, K, act, ldy, ldr, bm, bn, x2ptr, K1, H2, W2, C2, stride2,
-                        zero->data_ptr(), cur_stream());
-  } else {
-    rc = aiko_conv_igemm(x.data_ptr(), w.data_ptr(), bptr, rptr, y.data_ptr(), H, W, C, Cc, R, S, stride,
-                         pad, Ho, Wo, M, Cout, K, act, ldy, ldr, bm, bn, x2ptr, K1, H2, W2, C2, stride2,
-                         cur_stream());
+    case CONV_PERSIST:
+      TORCH_CHECK(buf_shape && K % 64 == 0,
+                  "aiko.conv_igemm_out: variant 4 needs Cc % 64 == 0, R*S <= 32 and operands < 2 GiB");
+      TORCH_CHECK(x2_fits, "aiko.conv_igemm_out: x2 too large for variant 4");
+      rc = aiko_conv_persist(&L);
+      break;
+    case CONV_NARROW:
+      TORCH_CHECK(!dual && ((R == 3 && S == 3 && pad == 1 && (stride == 1 || stride == 2)) ||
+                            (R == 1 && S == 1 && pad == 0 && stride == 1)) &&
+                      (Cc == 16 || Cc == 32) && (Cout == 16 || Cout == 32),
+                  "aiko.conv_igemm_out: variant 7 needs a 3x3 / pad 1 / stride 1-2 or 1x1 / stride 1 conv with Cc, Cout in {16, 32}");
+      // bm = output rows per workgroup (8 / 16); bn = 64: Cc-32 weights in registers
+      rc = aiko_conv_narrow(L.x, L.w, bptr, rptr, L.y, H, W, C, Cc, R, S, stride, pad, Ho, Wo, M, Cout, K, act, ldy,
+                            ldr, bm == 16 ? 16 : 8, bn == 64 ? 1 : 0, L.stream);
+      break;
+    case CONV_WIDE:
+    case CONV_WIDE_OCC:
+    case CONV_WIDE_DEEP:
+    case CONV_WIDE_EXACT_N:
+    case CONV_WIDE4_OCC:
+    case CONV_WIDE_PERSIST:
+      TORCH_CHECK(buf_shape, "aiko.conv_igemm_out: variant 8 needs Cc % 64 == 0, R*S <= 32 and operands < 2 GiB");
+      TORCH_CHECK(x2_fits, "aiko.conv_igemm_out: x2 too large for variant 8");
+      TORCH_CHECK(ldy % 8 == 0 && (!rptr || (ldr % 8 == 0 && reinterpret_cast<uintptr_t>(rptr) % 16 == 0)),
+                  "aiko.conv_igemm_out: variant 8 needs 16-B aligned rows");
+      // aiko_conv_wide's form: 1 = one workgroup per CU, 2 = several; the others go by their id
+      rc = aiko_conv_wide(&L, variant == CONV_WIDE ? 1 : variant == CONV_WIDE_OCC ? 2 : (int)variant);
+      break;
+    case CONV_PW:
+    case CONV_PW_RESIDENT:
+    case CONV_PW_RESIDENT_AB: {
+      static int cus = 0;
+      if (cus == 0) {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus = n;
+      }
+      if (variant == CONV_PW_RESIDENT && dual) {
+        // fused projection on the resident-weight kernel: 1x1 main source of 128 channels + a
+        // 1x1 / stride-s2 second source of 256 channels
+        TORCH_CHECK(R == 1 && S == 1 && stride == 1 && pad == 0 && Cc == 128 && K1 == 128 && K == 384 &&
+                        Cout % 128 == 0 && C % 8 == 0 && !rptr && x_extent * 2 < (1LL << 31) - 64 && x2_fits &&
+                        avail_elems(y) * 2 < (1LL << 31) && ldy % 8 == 0,
+                    "aiko.conv_igemm_out: variant 13 with a second source needs a 128 + 256 column 1x1 projection, "
+                    "Cout % 128 == 0, no residual and operands < 2 GiB");
+        TORCH_CHECK(!bptr || reinterpret_cast<uintptr_t>(bptr) % 16 == 0, "aiko.conv_igemm_out: bias alignment");
+        rc = aiko_conv_pw_dual(L.x, x2ptr, L.w, bptr, L.y, M, Cout, C, C2, ldy, act, Ho, Wo, H2, W2, stride2, cus,
+                               L.stream);
+        break;
+      }
+      // 1x1 / stride 1 / one source, x rows = pixels at pitch C
+      const bool pw_shape = variant == CONV_PW ? (K % 256 == 0 && Cout % 128 == 0)
+                                               : ((K == 128 && Cout % 256 == 0) || (K == 256 && Cout % 128 == 0) ||
+                                                  (K == 512 && Cout % 64 == 0));
+      TORCH_CHECK(!dual && R == 1 && S == 1 && stride == 1 && pad == 0 && Cc == K && pw_shape &&
+                      C % 8 == 0 && x_extent * 2 < (1LL << 31) - 64 && w.numel() * 2 < (1LL << 31) &&
+                      avail_elems(y) * 2 < (1LL << 31),
+                  "aiko.conv_igemm_out: variants 12/13 need a 1x1/s1 single-source conv with K % 256 == 0 "
+                  "(13: K = 128 / 256 / 512), Cout a multiple of the channel block and operands < 2 GiB");
+      TORCH_CHECK(ldy % 8 == 0 && (!rptr || (ldr % 8 == 0 && reinterpret_cast<uintptr_t>(rptr) % 16 == 0 &&
+                                            avail_elems(*res) * 2 < (1LL << 31) - 64)),
+                  "aiko.conv_igemm_out: variant 12 needs 16-B aligned rows");
+      TORCH_CHECK(!bptr || reinterpret_cast<uintptr_t>(bptr) % 16 == 0, "aiko.conv_igemm_out: bias alignment");
+      // mode: 0 streamed weights, 1 resident weight block, 2 resident with the residual at its own tile
+      rc = aiko_conv_pw(L.x, L.w, bptr, rptr, L.y, M, Cout, K, C, ldy, ldr, act, cus,
+                        variant == CONV_PW_RESIDENT ? 1 : variant == CONV_PW_RESIDENT_AB ? 2 : 0, L.stream);
+      break;
+    }
+    default:   // CONV_PATCH / PATCHW / ROWS have operators of their own
+      TORCH_CHECK(false, "aiko.conv_igemm_out: unknown variant ", variant);
   }
   check_launch(rc, "conv_igemm");
 }

@@ -2,6 +2,7 @@
 // global_load_lds variants).
 #pragma once
 #include "common.h"
+#include "conv_launch.h"
 
 namespace aiko {
 
@@ -45,6 +46,22 @@ __host__ inline void conv_params_finalize(ConvParams& p) {
   fastdiv_init(p.Wo, &p.mWo, &p.lWo);
   fastdiv_init(p.Cc, &p.mCc, &p.lCc);
   fastdiv_init(p.S, &p.mS, &p.lS);
+}
+
+__host__ inline ConvParams conv_params(const ConvLaunch& l) {
+  ConvParams p;
+  p.x = static_cast<const bf16_t*>(l.x);
+  p.w = static_cast<const bf16_t*>(l.w);
+  p.bias = l.bias;
+  p.res = static_cast<const bf16_t*>(l.res);
+  p.y = static_cast<bf16_t*>(l.y);
+  p.H = l.H; p.W = l.W; p.C = l.C; p.Cc = l.Cc; p.R = l.R; p.S = l.S;
+  p.stride = l.stride; p.pad = l.pad; p.Ho = l.Ho; p.Wo = l.Wo; p.M = l.M; p.Cout = l.Cout; p.K = l.K;
+  p.act = l.act; p.ldy = l.ldy; p.ldr = l.ldr;
+  p.x2 = static_cast<const bf16_t*>(l.x2);
+  p.K1 = l.x2 ? l.K1 : l.K; p.H2 = l.H2; p.W2 = l.W2; p.C2 = l.C2; p.stride2 = l.stride2;
+  conv_params_finalize(p);
+  return p;
 }
 
 }  // namespace aiko

@@ -301,24 +301,11 @@ __global__ __launch_bounds__(256, (conv_occupancy<BM, BN>())) void conv_igemm_ke
 
 }  // namespace aiko
 
-extern "C" int aiko_conv_igemm(const void* x, const void* w, const float* bias, const void* res,
-                               void* y, int H, int W, int C, int Cc, int R, int S,
-                               int stride, int pad, int Ho, int Wo, int M, int Cout, int K,
-                               int act, int ldy, int ldr, int bm, int bn, const void* x2, int K1,
-                               int H2, int W2, int C2, int stride2, hipStream_t stream) {
+extern "C" int aiko_conv_igemm(const ConvLaunch* l) {
   using namespace aiko;
-  ConvParams p;
-  p.x = static_cast<const bf16_t*>(x);
-  p.w = static_cast<const bf16_t*>(w);
-  p.bias = bias;
-  p.res = static_cast<const bf16_t*>(res);
-  p.y = static_cast<bf16_t*>(y);
-  p.H = H; p.W = W; p.C = C; p.Cc = Cc; p.R = R; p.S = S;
-  p.stride = stride; p.pad = pad; p.Ho = Ho; p.Wo = Wo; p.M = M; p.Cout = Cout; p.K = K;
-  p.act = act; p.ldy = ldy; p.ldr = ldr;
-  p.x2 = static_cast<const bf16_t*>(x2);
-  p.K1 = x2 ? K1 : K; p.H2 = H2; p.W2 = W2; p.C2 = C2; p.stride2 = stride2;
-  conv_params_finalize(p);
+  const int M = l->M, Cout = l->Cout, bm = l->bm, bn = l->bn;
+  hipStream_t stream = l->stream;
+  const ConvParams p = conv_params(*l);
   const int ntm = (M + bm - 1) / bm;
   const int ntn = (Cout + bn - 1) / bn;
   dim3 grid(ntm * ntn), block(256);

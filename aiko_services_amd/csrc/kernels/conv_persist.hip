@@ -340,27 +340,14 @@ static int cu_count() {
   return n;
 }
 
-// Same arguments as aiko_conv_buf (host preconditions identical: Cc and K-K1 multiples of 64,
-// R*S <= 32, operands < 2 GiB).  cfg selects the tile / ring / occupancy configuration.
-extern "C" int aiko_conv_persist(const void* x, const void* w, const float* bias, const void* res,
-                                 void* y, int H, int W, int C, int Cc, int R, int S, int stride,
-                                 int pad, int Ho, int Wo, int M, int Cout, int K, int act, int ldy,
-                                 int ldr, int bm, int bn, const void* x2, int K1, int H2, int W2,
-                                 int C2, int stride2, hipStream_t stream) {
+// Host preconditions as aiko_conv_buf (Cc and K-K1 multiples of 64, R*S <= 32, operands
+// < 2 GiB).  The tile selects the ring / occupancy configuration.
+extern "C" int aiko_conv_persist(const ConvLaunch* l) {
   using namespace aiko;
-  if (Cc % 64 || R * S > 32 || (x2 && (K - K1) % 64) || K % 64) return -1;
-  ConvParams p;
-  p.x = static_cast<const bf16_t*>(x);
-  p.w = static_cast<const bf16_t*>(w);
-  p.bias = bias;
-  p.res = static_cast<const bf16_t*>(res);
-  p.y = static_cast<bf16_t*>(y);
-  p.H = H; p.W = W; p.C = C; p.Cc = Cc; p.R = R; p.S = S;
-  p.stride = stride; p.pad = pad; p.Ho = Ho; p.Wo = Wo; p.M = M; p.Cout = Cout; p.K = K;
-  p.act = act; p.ldy = ldy; p.ldr = ldr;
-  p.x2 = static_cast<const bf16_t*>(x2);
-  p.K1 = x2 ? K1 : K; p.H2 = H2; p.W2 = W2; p.C2 = C2; p.stride2 = stride2;
-  conv_params_finalize(p);
+  const int M = l->M, Cout = l->Cout, bm = l->bm, bn = l->bn;
+  hipStream_t stream = l->stream;
+  if (l->Cc % 64 || l->R * l->S > 32 || (l->x2 && (l->K - l->K1) % 64) || l->K % 64) return -1;
+  const ConvParams p = conv_params(*l);
   const int tiles = ((M + bm - 1) / bm) * ((Cout + bn - 1) / bn);
   int occ;
   if (bm == 64 && bn == 128) occ = 2;

@@ -694,28 +694,17 @@ __global__ __launch_bounds__(64 * WGM * WGN, 1) void conv_wide_pers_kernel(ConvP
 }
 }  // namespace aiko
 
-// Same arguments as aiko_conv_buf (no occupancy / MFMA-shape options).  Host preconditions
+// occ selects the form (1: one workgroup per CU, 2: several, 11 / 18 / 19 / 20: the variant of
+// that number).  Host preconditions
 // (checked by the binding): Cc and, with a second source, K - K1 are multiples of 64; R*S <= 32;
 // Cout % 8 == 0; every operand fits 2^31 bytes.
-extern "C" int aiko_conv_wide(const void* x, const void* w, const float* bias, const void* res,
-                              void* y, int H, int W, int C, int Cc, int R, int S, int stride,
-                              int pad, int Ho, int Wo, int M, int Cout, int K, int act, int ldy,
-                              int ldr, int bm, int bn, const void* x2, int K1, int H2, int W2,
-                              int C2, int stride2, int occ, hipStream_t stream) {
+extern "C" int aiko_conv_wide(const ConvLaunch* l, int occ) {
   using namespace aiko;
-  if (Cc % 64 || R * S > 32 || R > 16 || S > 16 || (x2 && (K - K1) % 64) || Cout % 8) return -1;
-  ConvParams p;
-  p.x = static_cast<const bf16_t*>(x);
-  p.w = static_cast<const bf16_t*>(w);
-  p.bias = bias;
-  p.res = static_cast<const bf16_t*>(res);
-  p.y = static_cast<bf16_t*>(y);
-  p.H = H; p.W = W; p.C = C; p.Cc = Cc; p.R = R; p.S = S;
-  p.stride = stride; p.pad = pad; p.Ho = Ho; p.Wo = Wo; p.M = M; p.Cout = Cout; p.K = K;
-  p.act = act; p.ldy = ldy; p.ldr = ldr;
-  p.x2 = static_cast<const bf16_t*>(x2);
-  p.K1 = x2 ? K1 : K; p.H2 = H2; p.W2 = W2; p.C2 = C2; p.stride2 = stride2;
-  conv_params_finalize(p);
+  const int M = l->M, Cout = l->Cout, K = l->K, bm = l->bm, bn = l->bn;
+  const void* res = l->res;
+  hipStream_t stream = l->stream;
+  if (l->Cc % 64 || l->R * l->S > 32 || l->R > 16 || l->S > 16 || (l->x2 && (K - l->K1) % 64) || Cout % 8) return -1;
+  const ConvParams p = conv_params(*l);
   dim3 grid(((M + bm - 1) / bm) * ((Cout + bn - 1) / bn));
   if (occ == 18) {                    // exact-N tiles: bn = the channels computed per tile
     if (Cout % 16) return -1;

@@ -17,7 +17,9 @@ covers the 7 horizontal taps of one filter row, so the stem is an implicit GEMM 
 from __future__ import annotations
 
 import math
+import os
 from dataclasses import dataclass, field
+from enum import IntEnum
 
 import torch
 
@@ -192,7 +194,9 @@ TILES = ((128, 128), (128, 64), (64, 128), (64, 64))
 NARROW_TILES = ((128, 32), (256, 32), (64, 64), (128, 64))   # Cout <= 32 (YOLO stems / heads)
 _tile_cache: dict = {}          # geometry key -> (bm, bn), filled by autotune()
 _tuning = False
-_TUNE_VERBOSE = __import__("os").environ.get("AIKO_TUNE_VERBOSE", "0") == "1"
+_TUNE_VERBOSE = os.environ.get("AIKO_TUNE_VERBOSE", "0") == "1"
+
+
 class autotune:
     """Context manager: while active, every conv whose geometry has no cached tile times each
     candidate tile on the GPU (3 runs, HIP events) and keeps the fastest — like a conv
@@ -245,34 +249,39 @@ def zero_page(device) -> torch.Tensor:
     return z
 
 
-BUF_WIDE_TILES = ((256, 128), (128, 256), (256, 64))   # 8-wave buffer-DMA kernels (one workgroup per CU)
-BUF_OCC_TILES = ((64, 64), (64, 128), (128, 64))       # variant 3: buffer-DMA at 5 / 3 / 3 workgroups per CU
-PERSIST_TILES = ((64, 128),)   # variant 4: persistent, one K-block ring across tiles (2 workgroups/CU)
-# variant 5: buffer-DMA kernel on v_mfma_f32_32x32x16_bf16 (3x the free issue slots per MFMA)
-MF32_TILES = ((128, 128), (128, 64), (64, 128), (256, 128), (128, 256))
-# variant 6: 4 waves of 128 x 64 / 64 x 128 per workgroup, one workgroup per CU (fewer LDS
-# fragment bytes per MFMA than the 8-wave 64 x 64 layouts of BUF_WIDE_TILES).  Measured on the
-# ResNet-50 layers: never the tuner's pick — one wave per SIMD exposes the DMA / LDS latency
-# that the 8-wave layouts hide — kept as a candidate for other shapes
-WIDE4_TILES = ((256, 128), (128, 256))
-# variant 8 (conv_wide.hip): 8 waves, transposed product (weights on the MFMA A side) so each
-# lane ends with 8 consecutive output channels of one pixel and the epilogue goes straight from
-# registers to memory (no LDS round trip) — tiles up to 256 x 256
-WIDE8_TILES = ((256, 256), (256, 128), (128, 256), (256, 64), (128, 128))
-# variant 19: the same kernel with 4 waves of 64 x 64 (128 x 128 tile, 2 workgroups per CU) or
-# 64 x 128 (128 x 256, one per CU): half / a third fewer fragment reads per MFMA than the 8-wave
-# 128-wide forms, whose 64 x 32 wave tiles read 0.75 fragments per MFMA.  Measured at B=320
-# (round 5, scripts/r5_tiles.sh): stage-2 3x3 84.4 vs 81.2 us (variant 9), stage-3 3x3 79.9 vs
-# 66.0 us (variant 8) — the fragment traffic was not the limit; opt-in (AIKO_CONV_EXTRA=19)
-WIDE4_OCC_TILES = ((128, 128), (128, 256))
-# variant 20: persistent conv_wide (one workgroup per CU walks tiles with ONE K-block ring across
-# tile boundaries; epilogue stores always issued, so the next tile's first-block wait is exact)
-# for the short-K layers without a residual (reductions, projections).  Measured at B=320 (round
-# 5): fused stage-2 projection 159.6 vs 163.6 us (variant 8), stage-3 reduction 37.4 vs 36.1,
-# stage-3 -> 4 reduction 70.6 vs 66.1 — the tile-boundary fill was not the limit either; the
-# tuner keeps it where it wins (residual form, isolated at B=320: 60-61 vs 49.7 us at stage 4,
-# 87.6 vs 76.7 us at stage 3 against the resident-weight kernel)
-WIDE_PERS_TILES = ((256, 256), (256, 128), (128, 256))
+class Variant(IntEnum):
+    """Kernel ids of ``tile=(bm, bn, variant)``.  The integers are a persisted format (tile-cache
+    files, ``AIKO_CONV_SKIP`` / ``AIKO_CONV_EXTRA``, profiles) and are mirrored by ``ConvVariant``
+    in ``csrc/kernels/conv_launch.h``: a new kernel takes a new number, none is ever re-used."""
+    IGEMM = 0
+    GLDS = 1
+    BUF = 2
+    BUF_OCC = 3
+    PERSIST = 4
+    BUF_MF32 = 5
+    BUF_WIDE4 = 6
+    NARROW = 7
+    WIDE = 8
+    WIDE_OCC = 9
+    PATCH = 10
+    WIDE_DEEP = 11
+    PW = 12
+    PW_RESIDENT = 13
+    PW_RESIDENT_AB = 14
+    PATCHW = 16
+    ROWS = 17
+    WIDE_EXACT_N = 18
+    WIDE4_OCC = 19
+    WIDE_PERSIST = 20
+
+
+@dataclass(frozen=True)
+class VariantInfo:
+    kernel: str                     # file under csrc/kernels/
+    tiles: tuple                    # every (bm, bn) the tuner may offer, in the order it times them
+    extra: bool = False             # opt-in: tuned only when AIKO_CONV_EXTRA names the id
+
+
 # variant 18: the same kernel with an exact-N tile (the MFMAs and epilogue cover exactly
 # these channel counts — the YOLO head's 80-class and 64 + 80 box/class convs — instead of
 # rounding N up to a 128 / 192 tile; odd 16-channel block counts end in an 8-byte store)
@@ -281,33 +290,92 @@ EXACT_N = (80, 144)
 # for N = 80 layers whose 80-channel input (Cc = 80) rules out every 64-channel-block kernel: the
 # YOLOv8 class branch (3x3 80 -> 80, 1x1 80 -> 80), where a 128-wide tile wastes 37.5 % of its lanes
 GLDS_EXACT_N = (80,)
-# variant 9: the same kernel at 2-3 workgroups per CU (short-K, bandwidth-bound layers)
-WIDE_OCC_TILES = ((128, 128), (256, 64), (128, 64), (64, 128), (64, 64))
-# variant 11: the same kernel with 32-deep K blocks in a 4-slot ring (three blocks in flight
-# across each barrier instead of one for the 256-wide tiles) — the long-K compute-bound layers.
-# Measured on the ResNet-50 layers (MI355X, round 3): never the tuner's pick against variant 8,
-# i.e. the 2-slot 64-deep ring is not what limits those tiles; kept as a candidate.  Round 4: a
-# 256 x 256 form with split rings (3 activation slots + 2 weight slots = 160 KB, activations two
-# blocks ahead) measured 70.8 vs 68.0 us on the stage-3 3x3 (PMC of variant 11 vs 8: wait share
-# 37 vs 40 %, twice the L2 requests at 64-B rows) — dropped
-WIDE_DEEP_TILES = ((256, 256), (256, 128), (128, 256))
-# variant 12 (conv_pw.hip): persistent pointwise GEMM for 1x1/s1 convs with K % 256 == 0 — one
-# 4-slot K-block ring across tile boundaries, residual DMA'd into LDS, fixed channel block per
-# workgroup; 77.9 vs 80 us on the stage-3 expansion at B=320.  Variant 13 (K == 256): the
-# workgroup's 128 x 256 weight block resident in LDS, 64-pixel tiles through an 8-slot ring (seven
-# blocks in flight): 65.6 us there (the tuner's pick; 500 TF, 4.4 TB/s counting the residual).
-# Round 4: variant 13 also takes K == 128 (256 x 128 weight block, 4-slot ring) and DMAs the residual
-# one tile ahead; variant 14 is the same kernel with the residual issued at its own tile (A/B form,
-# tuned only with AIKO_PW_AB=1).  Measured at B=320 (scripts/pw_check.sh, same box): K=128 -> 512
-# expansion 105.5 (13) vs 110.9 us (14) and vs 133 us for the best tiled kernel (5.6 TB/s counting the
-# residual); K=256 -> 1024 71.4 vs 71.8; K=512 -> 2048 81.1 vs 79.8 (the tiled kernel, 47 us, wins)
-_PW_AB = __import__("os").environ.get("AIKO_PW_AB") == "1"
-# opt-in tuner variants (never picked on the measured models): AIKO_CONV_EXTRA="6,11"
-_EXTRA = {int(v) for v in __import__("os").environ.get("AIKO_CONV_EXTRA", "").split(",") if v.strip().isdigit()}
-# variant 13 as the fused stage-2 projection (conv_pw_rb_kernel<false, 384, 1, 128>) in the tuner:
-# numerics-tested but measured slower than conv_wide's 256 x 256 tile (167 vs 154 us at B=320 — the
-# strided second source streams from HBM behind a 5-block lookahead), so opt-in
-_PW_DUAL = __import__("os").environ.get("AIKO_PW_DUAL", "0") == "1"
+
+VARIANTS: dict[Variant, VariantInfo] = {
+    # register-staged implicit GEMM; Cout <= 32 is offered NARROW_TILES instead of TILES
+    Variant.IGEMM: VariantInfo("conv_igemm.hip", TILES + NARROW_TILES[:2]),
+    # LDS-DMA kernel (needs the zero page): TILES, plus (128, N) and (256, N) for N in GLDS_EXACT_N
+    Variant.GLDS: VariantInfo("conv_glds.hip", TILES + tuple((bm, n) for n in GLDS_EXACT_N for bm in (128, 256))),
+    # buffer-LDS-DMA kernel; the last three are its 8-wave forms (one workgroup per CU)
+    Variant.BUF: VariantInfo("conv_buf.hip", TILES + ((256, 128), (128, 256), (256, 64))),
+    # variant 3: buffer-DMA at 5 / 3 / 3 workgroups per CU
+    Variant.BUF_OCC: VariantInfo("conv_buf.hip", ((64, 64), (64, 128), (128, 64))),
+    # variant 4: persistent, one K-block ring across tiles (2 workgroups/CU)
+    Variant.PERSIST: VariantInfo("conv_persist.hip", ((64, 128),)),
+    # variant 5: buffer-DMA kernel on v_mfma_f32_32x32x16_bf16 (3x the free issue slots per MFMA)
+    # variant 5 wins some ResNet layers in isolation, but the two-lane bench is ~1 % faster
+    # without it (90.3k vs 91.4k frames/s, 5 + 5 interleaved runs on two boxes,
+    # scripts/r5_skip_ab.sh; YOLO / Whisper never pick it): opt-in, AIKO_CONV_EXTRA=5
+    Variant.BUF_MF32: VariantInfo("conv_buf.hip", ((128, 128), (128, 64), (64, 128), (256, 128), (128, 256)),
+                                  extra=True),
+    # variant 6: 4 waves of 128 x 64 / 64 x 128 per workgroup, one workgroup per CU (fewer LDS
+    # fragment bytes per MFMA than the 8-wave 64 x 64 layouts of variant 2's wide tiles).  Measured on the
+    # ResNet-50 layers: never the tuner's pick — one wave per SIMD exposes the DMA / LDS latency
+    # that the 8-wave layouts hide — kept as a candidate for other shapes
+    # variants 6 and 11 were never the tuner's pick on any layer measured (rounds 3-4):
+    # out of default tuning (setup time), kept for other shapes behind AIKO_CONV_EXTRA=6,11
+    Variant.BUF_WIDE4: VariantInfo("conv_buf.hip", ((256, 128), (128, 256)), extra=True),
+    # variant 7: 8 x 32 / 16 x 32 output pixels per workgroup; bn = 64: Cc-32 weights held in
+    # registers, not LDS
+    Variant.NARROW: VariantInfo("conv_narrow.hip", ((8, 32), (16, 32), (8, 64), (16, 64))),
+    # variant 8 (conv_wide.hip): 8 waves, transposed product (weights on the MFMA A side) so each
+    # lane ends with 8 consecutive output channels of one pixel and the epilogue goes straight from
+    # registers to memory (no LDS round trip) — tiles up to 256 x 256
+    Variant.WIDE: VariantInfo("conv_wide.hip", ((256, 256), (256, 128), (128, 256), (256, 64), (128, 128))),
+    # variant 9: the same kernel at 2-3 workgroups per CU (short-K, bandwidth-bound layers)
+    Variant.WIDE_OCC: VariantInfo("conv_wide.hip", ((128, 128), (256, 64), (128, 64), (64, 128), (64, 64))),
+    # variant 10: tile fixed by the kernel (8 rows x W)
+    Variant.PATCH: VariantInfo("conv_patch.hip", ((8, 64),)),
+    # variant 11: the same kernel with 32-deep K blocks in a 4-slot ring (three blocks in flight
+    # across each barrier instead of one for the 256-wide tiles) — the long-K compute-bound layers.
+    # Measured on the ResNet-50 layers (MI355X, round 3): never the tuner's pick against variant 8,
+    # i.e. the 2-slot 64-deep ring is not what limits those tiles; kept as a candidate.  Round 4: a
+    # 256 x 256 form with split rings (3 activation slots + 2 weight slots = 160 KB, activations two
+    # blocks ahead) measured 70.8 vs 68.0 us on the stage-3 3x3 (PMC of variant 11 vs 8: wait share
+    # 37 vs 40 %, twice the L2 requests at 64-B rows) — dropped
+    Variant.WIDE_DEEP: VariantInfo("conv_wide.hip", ((256, 256), (256, 128), (128, 256)), extra=True),
+    # variant 12 (conv_pw.hip): persistent pointwise GEMM for 1x1/s1 convs with K % 256 == 0 — one
+    # 4-slot K-block ring across tile boundaries, residual DMA'd into LDS, fixed channel block per
+    # workgroup; 77.9 vs 80 us on the stage-3 expansion at B=320.  Variant 13 (K == 256): the
+    # workgroup's 128 x 256 weight block resident in LDS, 64-pixel tiles through an 8-slot ring (seven
+    # blocks in flight): 65.6 us there (the tuner's pick; 500 TF, 4.4 TB/s counting the residual).
+    # Round 4: variant 13 also takes K == 128 (256 x 128 weight block, 4-slot ring) and DMAs the residual
+    # one tile ahead; variant 14 is the same kernel with the residual issued at its own tile (A/B form,
+    # tuned only with AIKO_PW_AB=1).  Measured at B=320 (scripts/pw_check.sh, same box): K=128 -> 512
+    # expansion 105.5 (13) vs 110.9 us (14) and vs 133 us for the best tiled kernel (5.6 TB/s counting the
+    # residual); K=256 -> 1024 71.4 vs 71.8; K=512 -> 2048 81.1 vs 79.8 (the tiled kernel, 47 us, wins)
+    Variant.PW: VariantInfo("conv_pw.hip", ((128, 128),)),
+    # variant 13 as the fused stage-2 projection (conv_pw_rb_kernel<false, 384, 1, 128>) in the tuner:
+    # numerics-tested but measured slower than conv_wide's 256 x 256 tile (167 vs 154 us at B=320 — the
+    # strided second source streams from HBM behind a 5-block lookahead), so opt-in (AIKO_PW_DUAL=1)
+    Variant.PW_RESIDENT: VariantInfo("conv_pw.hip", ((64, 128),)),
+    Variant.PW_RESIDENT_AB: VariantInfo("conv_pw.hip", ((64, 128),)),
+    # variant 16: 14-row patch tiles, streamed weights
+    Variant.PATCHW: VariantInfo("conv_patchw.hip", ((392, 128),)),
+    # variant 17: persistent row stream (80-wide 32 -> 32 3x3)
+    Variant.ROWS: VariantInfo("conv_rows.hip", ((1, 32),)),
+    # variant 18: (256, N) then (128, N) for N in EXACT_N (see EXACT_N above)
+    Variant.WIDE_EXACT_N: VariantInfo("conv_wide.hip", tuple((bm, n) for n in EXACT_N for bm in (256, 128))),
+    # variant 19: the same kernel with 4 waves of 64 x 64 (128 x 128 tile, 2 workgroups per CU) or
+    # 64 x 128 (128 x 256, one per CU): half / a third fewer fragment reads per MFMA than the 8-wave
+    # 128-wide forms, whose 64 x 32 wave tiles read 0.75 fragments per MFMA.  Measured at B=320
+    # (round 5, scripts/r5_tiles.sh): stage-2 3x3 84.4 vs 81.2 us (variant 9), stage-3 3x3 79.9 vs
+    # 66.0 us (variant 8) — the fragment traffic was not the limit; opt-in (AIKO_CONV_EXTRA=19)
+    Variant.WIDE4_OCC: VariantInfo("conv_wide.hip", ((128, 128), (128, 256)), extra=True),
+    # variant 20: persistent conv_wide (one workgroup per CU walks tiles with ONE K-block ring across
+    # tile boundaries; epilogue stores always issued, so the next tile's first-block wait is exact)
+    # for the short-K layers without a residual (reductions, projections).  Measured at B=320 (round
+    # 5): fused stage-2 projection 159.6 vs 163.6 us (variant 8), stage-3 reduction 37.4 vs 36.1,
+    # stage-3 -> 4 reduction 70.6 vs 66.1 — the tile-boundary fill was not the limit either; the
+    # tuner keeps it where it wins (residual form, isolated at B=320: 60-61 vs 49.7 us at stage 4,
+    # 87.6 vs 76.7 us at stage 3 against the resident-weight kernel)
+    # variant 20: at B=320 the ResNet bench ran 1 % faster without it (89.8k vs 90.7k,
+    # round 5, scripts/r5_skip_ab.sh); at the round-6 default B=640, interleaved on two
+    # boxes: 94.6k / 94.2k with vs 93.2k / 93.2k without, then 92.63-92.70k vs
+    # 92.64-92.86k (YOLOv8-n 50.0k both): default again, AIKO_CONV_SKIP=20 leaves it out
+    # With a residual (K >= 192 only): the 3-slot forms, i.e. without the 256 x 256 tile
+    Variant.WIDE_PERSIST: VariantInfo("conv_wide.hip", ((256, 256), (256, 128), (128, 256))),
+}
 
 
 def buf_variant_ok(spec: ConvSpec, x: torch.Tensor, x2: torch.Tensor | None = None) -> bool:
@@ -459,66 +527,71 @@ def narrow_variant_ok(spec: ConvSpec, x2: torch.Tensor | None = None) -> bool:
             and spec.Cc in (16, 32) and spec.cout in (16, 32))
 
 
-def _tune(key, M, cout, launch, buf_ok=False, narrow_ok=False, patch_ok=False, pw_ok=False, has_res=False,
-          patchw_ok=False, rows_ok=False):
-    if cout <= 32:
-        cands = [t + (0,) for t in NARROW_TILES]
-        if narrow_ok:
-            cands.append((8, 32, 7))         # variant 7: 8 x 32 output pixels per workgroup
-            cands.append((16, 32, 7))        #            16 x 32
-            cands.append((8, 64, 7))         # bn = 64: Cc-32 weights held in registers, not LDS
-            cands.append((16, 64, 7))
-        if rows_ok:
-            cands.append((1, 32, 17))        # variant 17: persistent row stream (80-wide 32 -> 32 3x3)
-    else:
-        cands = [t + (0,) for t in TILES] + [t + (1,) for t in TILES]
-        if cout in GLDS_EXACT_N:
-            cands += [t + (1,) for t in ((128, cout), (256, cout))]
-        if buf_ok:
-            cands += [t + (2,) for t in TILES + BUF_WIDE_TILES] + [t + (3,) for t in BUF_OCC_TILES]
-            cands += [t + (4,) for t in PERSIST_TILES]
-            if 5 in _EXTRA:
-                # variant 5 wins some ResNet layers in isolation, but the two-lane bench is ~1 % faster
-                # without it (90.3k vs 91.4k frames/s, 5 + 5 interleaved runs on two boxes,
-                # scripts/r5_skip_ab.sh; YOLO / Whisper never pick it): opt-in, AIKO_CONV_EXTRA=5
-                cands += [t + (5,) for t in MF32_TILES]
-            cands += [t + (8,) for t in WIDE8_TILES] + [t + (9,) for t in WIDE_OCC_TILES]
-            if 19 in _EXTRA:
-                cands += [t + (19,) for t in WIDE4_OCC_TILES]
-            # variant 20: at B=320 the ResNet bench ran 1 % faster without it (89.8k vs 90.7k,
-            # round 5, scripts/r5_skip_ab.sh); at the round-6 default B=640, interleaved on two
-            # boxes: 94.6k / 94.2k with vs 93.2k / 93.2k without, then 92.63-92.70k vs
-            # 92.64-92.86k (YOLOv8-n 50.0k both): default again, AIKO_CONV_SKIP=20 leaves it out
-            if cout <= 2048 and not has_res:
-                cands += [t + (20,) for t in WIDE_PERS_TILES]
-            elif cout <= 2048 and key[2] >= 192:   # with a residual: 3-slot forms
-                cands += [t + (20,) for t in WIDE_PERS_TILES if t != (256, 256)]
-            if cout in EXACT_N:
-                cands += [(256, cout, 18), (128, cout, 18)]
-            # variants 6 and 11 were never the tuner's pick on any layer measured (rounds 3-4):
-            # out of default tuning (setup time), kept for other shapes behind AIKO_CONV_EXTRA=6,11
-            if 6 in _EXTRA:
-                cands += [t + (6,) for t in WIDE4_TILES]
-            if 11 in _EXTRA:
-                cands += [t + (11,) for t in WIDE_DEEP_TILES]
+def conv_candidates(spec: ConvSpec, x: torch.Tensor, residual=None, x2=None, out=None,
+                    residual_after_act: bool = False) -> list:
+    """Every ``(bm, bn, variant)`` the tuner times for this call, in timing order (the first of
+    equal times wins).  Pure: looks at shapes and strides only, so CPU and meta tensors do.
 
-        if patch_ok:
-            cands.append((8, 64, 10))        # variant 10: tile fixed by the kernel (8 rows x W)
-        if patchw_ok:
-            cands.append((392, 128, 16))     # variant 16: 14-row patch tiles, streamed weights
+    Switches, read at call time: ``AIKO_CONV_EXTRA="6,11"`` adds opt-in variants (``extra`` in
+    :data:`VARIANTS`: never picked on the measured models), ``AIKO_PW_AB=1`` adds
+    ``PW_RESIDENT_AB`` next to ``PW_RESIDENT``, ``AIKO_PW_DUAL=1`` offers ``PW_RESIDENT`` for the
+    fused stage-2 projection; ``AIKO_CONV_SKIP="8,20"`` and ``AIKO_CONV_SKIP_TILES="256x192x8"``
+    (A/B runs) leave variants / exact tiles out unless that would leave nothing."""
+    V = Variant
+    extra = {int(v) for v in os.environ.get("AIKO_CONV_EXTRA", "").split(",") if v.strip().isdigit()}
+    if spec.K1 is None:
+        x2 = None
+    has_res = residual is not None
+    cout = spec.cout
+
+    def of(v, tiles=None):
+        if VARIANTS[v].extra and v not in extra:
+            return []
+        return [(bm, bn, int(v)) for bm, bn in (VARIANTS[v].tiles if tiles is None else tiles)]
+
+    if cout <= 32:
+        cands = of(V.IGEMM, NARROW_TILES)
+        if narrow_variant_ok(spec, x2):
+            cands += of(V.NARROW)
+        if rows_variant_ok(spec, x, residual, x2, out):
+            cands += of(V.ROWS)
+    else:
+        cands = of(V.IGEMM, TILES) + of(V.GLDS, TILES)
+        if cout in GLDS_EXACT_N:
+            cands += of(V.GLDS, ((128, cout), (256, cout)))
+        if buf_variant_ok(spec, x, x2):
+            cands += of(V.BUF) + of(V.BUF_OCC) + of(V.PERSIST) + of(V.BUF_MF32) + of(V.WIDE) + of(V.WIDE_OCC)
+            cands += of(V.WIDE4_OCC)
+            if cout <= 2048 and not has_res:
+                cands += of(V.WIDE_PERSIST)
+            elif cout <= 2048 and spec.K >= 192:   # with a residual: 3-slot forms
+                cands += of(V.WIDE_PERSIST, [t for t in VARIANTS[V.WIDE_PERSIST].tiles if t != (256, 256)])
+            if cout in EXACT_N:
+                cands += of(V.WIDE_EXACT_N, ((256, cout), (128, cout)))
+            cands += of(V.BUF_WIDE4) + of(V.WIDE_DEEP)
+        if patch_variant_ok(spec, x, residual, x2, out) and not residual_after_act:
+            cands += of(V.PATCH)
+        if patchw_variant_ok(spec, x, residual, x2, out) and not residual_after_act:
+            cands += of(V.PATCHW)
+        pw_ok = pw_variant_ok(spec, x, x2)
         if pw_ok and pw_ok not in ("resident_only", "dual"):
-            cands.append((128, 128, 12))     # variant 12: persistent pointwise GEMM (conv_pw.hip)
-        if pw_ok in ("resident", "resident_only") or (pw_ok == "dual" and not has_res and _PW_DUAL):
-            cands.append((64, 128, 13))      # variant 13: the same with the weight block resident in LDS
-            if has_res and _PW_AB:
-                cands.append((64, 128, 14))  # variant 14: variant 13 with each tile's residual issued at its own tile
-    skip = {int(v) for v in __import__("os").environ.get("AIKO_CONV_SKIP", "").split(",") if v.strip()}
+            cands += of(V.PW)
+        if pw_ok in ("resident", "resident_only") or (
+                pw_ok == "dual" and not has_res and os.environ.get("AIKO_PW_DUAL", "0") == "1"):
+            cands += of(V.PW_RESIDENT)
+            if has_res and os.environ.get("AIKO_PW_AB") == "1":
+                cands += of(V.PW_RESIDENT_AB)
+    skip = {int(v) for v in os.environ.get("AIKO_CONV_SKIP", "").split(",") if v.strip()}
     if skip:                                   # A/B runs: exclude variants from the tuner
-        cands = [t for t in cands if (t[2] if len(t) > 2 else 0) not in skip] or cands
-    skip_t = {tuple(int(v) for v in e.split("x")) for e in __import__("os").environ.get("AIKO_CONV_SKIP_TILES", "").split(",")
+        cands = [t for t in cands if t[2] not in skip] or cands
+    skip_t = {tuple(int(v) for v in e.split("x")) for e in os.environ.get("AIKO_CONV_SKIP_TILES", "").split(",")
               if e.strip()}                    # exact tiles, e.g. AIKO_CONV_SKIP_TILES=256x192x8
     if skip_t:
-        cands = [t for t in cands if tuple(t) not in skip_t] or cands
+        cands = [t for t in cands if t not in skip_t] or cands
+    return cands
+
+
+def _tune(key, cands, launch):
     # each candidate: 2 warm launches, then the median of 5 individually timed ones (a 3-launch
     # sum was noisy enough to rank a 56 us kernel behind an 80 us one on a fresh box)
     best, best_t = None, None
@@ -533,7 +606,7 @@ def _tune(key, M, cout, launch, buf_ok=False, narrow_ok=False, patch_ok=False, p
         evs[-1][1].synchronize()
         ms = sorted(e0.elapsed_time(e1) for e0, e1 in evs)[2]
         if _TUNE_VERBOSE:
-            print(f"[tune] M={M} N={cout} {t}: {ms * 1e3:.1f} us", flush=True)
+            print(f"[tune] M={key[0]} N={key[1]} {t}: {ms * 1e3:.1f} us", flush=True)
         if best_t is None or ms < best_t:
             best, best_t = t, ms
     _tile_cache[key] = best
@@ -596,37 +669,33 @@ def conv2d(x: torch.Tensor, spec: ConvSpec, residual: torch.Tensor | None = None
             0 if residual is None else (residual.stride(2) if residual.dim() == 4 else residual.stride(0))]
 
     def launch(t):
-        # t = (BM, BN) or (BM, BN, variant): variant 1 = LDS-DMA kernel (needs the zero page),
-        # 2 = buffer-LDS-DMA kernel
-        v = t[2] if len(t) > 2 else 0
-        if v == 10:
+        # t = (BM, BN) or (BM, BN, variant), see VARIANTS; GLDS needs the zero page
+        v = t[2] if len(t) > 2 else Variant.IGEMM
+        if v == Variant.PATCH:
             if not patch_variant_ok(spec, x, residual, x2, out):
                 raise ValueError("conv2d: variant 10 needs a 3x3/s1/p1 64->64 conv on a contiguous W<=56 input")
             torch.ops.aiko.conv3x3_patch_out(x, patch_weight(spec), spec.bias, out, spec.act, 0)
             return
-        if v == 17:
+        if v == Variant.ROWS:
             if not rows_variant_ok(spec, x, residual, x2, out):
                 raise ValueError("conv2d: variant 17 needs a 3x3/s1/p1 32->32 conv on 80-wide row-strided views")
             torch.ops.aiko.conv3x3_rows_out(x, rows_weight(spec), spec.bias, residual, out, act, 0)
             return
-        if v == 16:
+        if v == Variant.PATCHW:
             if not patchw_variant_ok(spec, x, residual, x2, out):
                 raise ValueError("conv2d: variant 16 needs a 3x3/s1/p1 128->128 conv on a [B, H, 28, >=128] input")
             torch.ops.aiko.conv3x3_patchw_out(x, patchw_weight(spec), spec.bias, out, spec.act, 0)
             return
         torch.ops.aiko.conv_igemm_out(x, x2, spec.weight, spec.bias, residual, out,
-                                      head + [t[0], t[1]] + src2 + [v], zero_page(x.device) if v == 1 else None)
+                                      head + [t[0], t[1]] + src2 + [int(v)],
+                                      zero_page(x.device) if v == Variant.GLDS else None)
 
     if tile is None:
         key = (M, spec.cout, spec.K, spec.R, spec.S, spec.stride, pitch, spec.K1, residual is not None, spec.Cc)
         tile = _tile_cache.get(key)
         if tile is None:
             if _tuning:
-                tile = _tune(key, M, spec.cout, launch, buf_variant_ok(spec, x, x2), narrow_variant_ok(spec, x2),
-                             patch_variant_ok(spec, x, residual, x2, out) and not residual_after_act,
-                             pw_variant_ok(spec, x, x2), residual is not None,
-                             patchw_variant_ok(spec, x, residual, x2, out) and not residual_after_act,
-                             rows_variant_ok(spec, x, residual, x2, out))
+                tile = _tune(key, conv_candidates(spec, x, residual, x2, out, residual_after_act), launch)
             else:
                 tile = pick_tile(M, spec.cout)
     launch(tile)
@@ -726,7 +795,7 @@ def stem_pool_u8(frames: torch.Tensor, spec: ConvSpec, mean, std, out: torch.Ten
 
 
 LINEAR_SPLITK = 4     # K slices of the split-K linear (linear_splitk.hip)
-_LINEAR_SPLITK_ON = __import__("os").environ.get("AIKO_FC_SPLITK", "1") != "0"
+_LINEAR_SPLITK_ON = os.environ.get("AIKO_FC_SPLITK", "1") != "0"
 
 
 def linear_splitk_ok(x: torch.Tensor, spec: ConvSpec, residual=None) -> bool:

@@ -147,7 +147,7 @@ def linear_fp8(xq: torch.Tensor, xs: torch.Tensor | None, lin: Fp8Linear, out: t
         if tile is None:
             launch = lambda t: _launch(xq, xs, lin, out, residual, act, t, x_mx, out_mx)  # noqa: E731
             if _conv._tuning:
-                tile = _tune_fp8(key, launch, mx)
+                tile = _tune_fp8(key, fp8_candidates(key, mx), launch)
             else:
                 tile = (128, 128, 1) if mx else pick_tile(M, lin.n) + (1,)
     _launch(xq, xs, lin, out, residual, act, tile, x_mx, out_mx)
@@ -166,9 +166,9 @@ _tile_cache: dict = {}
 FP8_TILES = ((128, 128), (128, 64), (64, 128), (64, 64))
 
 
-def _tune_fp8(key, launch, mx=False):
-    """Pick (BM, BN, variant) by measurement, like ``ops.conv.autotune`` (shares its switch)."""
-    best, best_t = None, None
+def fp8_candidates(key, mx=False) -> list:
+    """Every (BM, BN, variant) the fp8 tuner times for ``key`` (see :func:`linear_fp8`), in timing
+    order.  Pure; ``AIKO_FP8_SKIP`` is read at call time."""
     if mx:                               # MX-fp8 in/out: LDS-DMA kernels, whole 128-wide K chunks
         cands = [(128, 128, 1), (64, 128, 1)]
     else:
@@ -194,7 +194,12 @@ def _tune_fp8(key, launch, mx=False):
             cands.append((128, 256, 5))
     # AIKO_FP8_SKIP="256x256x4,128x256x5": candidates (BM x BN x variant) the tuner leaves out
     skip = {s.strip() for s in os.environ.get("AIKO_FP8_SKIP", "").split(",") if s.strip()}
-    cands = [t for t in cands if "x".join(map(str, t)) not in skip] or cands
+    return [t for t in cands if "x".join(map(str, t)) not in skip] or cands
+
+
+def _tune_fp8(key, cands, launch):
+    """Pick (BM, BN, variant) by measurement, like ``ops.conv.autotune`` (shares its switch)."""
+    best, best_t = None, None
     for t in cands:
         try:
             launch(t)

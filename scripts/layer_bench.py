@@ -70,9 +70,8 @@ def main():
         res[name] = {}
         cands = [tt + (0,) for tt in base] + ([tt + (1,) for tt in base] if cout > 32 else [])
         if cout > 32 and C.buf_variant_ok(spec, x, x2):
-            cands += [tt + (2,) for tt in base + C.BUF_WIDE_TILES] + [tt + (3,) for tt in C.BUF_OCC_TILES]
-            cands += [tt + (4,) for tt in C.PERSIST_TILES]
-            cands += [tt + (5,) for tt in C.MF32_TILES]
+            for v in (C.Variant.BUF, C.Variant.BUF_OCC, C.Variant.PERSIST, C.Variant.BUF_MF32):
+                cands += [tt + (int(v),) for tt in C.VARIANTS[v].tiles]
         if a.tile:
             cands = [tuple(int(v) for v in a.tile.split(","))]
         for t in cands:

@@ -205,6 +205,22 @@ def test_conv_igemm_matches_torch(native, B, H, W, cin, cout, k, stride, pad, ac
     assert err < 1e-2, err
 
 
+@pytest.mark.parametrize("tile,message", [((64, 64, 15), "unknown variant 15"),          # no such id
+                                          ((64, 64, 8), "unsupported configuration")])   # no such tile
+def test_conv_rejects_unknown_variant_and_tile(native, tile, message):
+    """An id without a kernel, or a tile its kernel does not have, is refused on the host: it
+    raises (naming the variant / the configuration) and launches nothing — ``out`` keeps its
+    sentinel.  It never runs another kernel instead."""
+    from aiko_services_amd.ops import conv as C
+    spec = C.make_conv_spec(torch.ones(64, 64, 1, 1), torch.ones(64), device=DEV)
+    x = torch.ones(1, 4, 4, 64, dtype=torch.bfloat16, device=DEV)
+    out = torch.full((1, 4, 4, 64), -7.0, dtype=torch.bfloat16, device=DEV)
+    with pytest.raises(RuntimeError, match=message):
+        C.conv2d(x, spec, out=out, tile=tile)
+    torch.cuda.synchronize()
+    assert (out == -7.0).all().item()
+
+
 @pytest.mark.parametrize("B,H,act,res,slices,grid", [
     (2, 80, "silu", None, False, 0), (3, 80, "silu", "after", True, 0), (1, 7, "relu", "before", False, 0),
     (4, 3, "silu", None, True, 5), (2, 1, None, "after", False, 1), (64, 80, "silu", "after", True, 0),
