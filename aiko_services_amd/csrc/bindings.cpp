@@ -79,6 +79,8 @@ int aiko_motion_detect(const void* frames, const int* bg, const int* seen, int* 
                        int learn_shift, int learn_moving, int warmup, int min_cells, int max_det, hipStream_t stream);
 int aiko_jpeg_encode(const void* raw, const void* tables, int header_len, void* workspace, void* stream, int* nbytes,
                      int B, int H, int W, int fmt, long cap, int seg_cap, hipStream_t stream_);
+int aiko_jpeg_decode(const void* data, const int* nbytes, const void* desc, int desc_rows, void* workspace, void* raw,
+                     int* status, int B, int H, int W, int fmt, long cap, int max_int, hipStream_t stream_);
 int aiko_batchnorm(const void* x, void* y, const float* scale, const float* shift, long P, int C, int ldx,
                    int ldy, int act, hipStream_t stream);
 int aiko_upsample2x(const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy,
@@ -1568,6 +1570,64 @@ void jpeg_encode_out(const at::Tensor& raw, int64_t height, int64_t width, int64
                "jpeg_encode");
 }
 
+// Baseline JPEG decoding (jpeg_decode_ops.hip; the rule, the descriptor and the workspace are in
+// ops/jpeg_decode.py): one stream per row of data [B, cap], its length in nbytes [B], its header's descriptor
+// in desc [B, 1744] or [1, 1744] (one for all) -> raw frames [B, frame_bytes] (fmt 1: i420, 2: i444, 3: yuyv) and
+// a status per frame.  max_intervals: the restart intervals per frame provided for.  Three launches on the
+// current stream
+void jpeg_decode_out(const at::Tensor& data, const at::Tensor& nbytes, const at::Tensor& desc, int64_t height,
+                     int64_t width, int64_t fmt, int64_t max_intervals, at::Tensor& raw, at::Tensor& status,
+                     at::Tensor& workspace) {
+  const at::Tensor* ts[6] = {&data, &nbytes, &desc, &raw, &status, &workspace};
+  const char* names[6] = {"data", "nbytes", "desc", "raw", "status", "workspace"};
+  for (int i = 0; i < 6; ++i) check_cuda(*ts[i], names[i]);
+  for (int i = 1; i < 6; ++i)
+    TORCH_CHECK(ts[i]->device() == data.device(), "aiko.jpeg_decode_out: tensors on different devices");
+  TORCH_CHECK(fmt == 1 || fmt == 2 || fmt == 3, "aiko.jpeg_decode_out: fmt 1 (i420), 2 (i444) or 3 (yuyv) required, got ",
+              fmt);
+  TORCH_CHECK(height >= 1 && height <= 65535 && width >= 1 && width <= 4096,
+              "aiko.jpeg_decode_out: 1 <= height <= 65535 and 1 <= width <= 4096 required, got ", height, " x ", width);
+  TORCH_CHECK(fmt != 3 || width % 2 == 0, "aiko.jpeg_decode_out: yuyv needs an even width, got ", width);
+  const int64_t H = height, W = width, mh = fmt == 1 ? 16 : 8, mw = fmt == 2 ? 8 : 16;
+  const int64_t mcus = ((H + mh - 1) / mh) * ((W + mw - 1) / mw);
+  const int64_t nblocks = mcus * (fmt == 1 ? 6 : (fmt == 2 ? 3 : 4));
+  const int64_t frame = fmt == 1 ? H * W + 2 * ((H + 1) / 2) * ((W + 1) / 2) : (fmt == 2 ? 3 * H * W : 2 * H * W);
+  TORCH_CHECK(max_intervals >= 1 && max_intervals <= mcus, "aiko.jpeg_decode_out: 1 <= max_intervals <= ", mcus,
+              " (the frame's MCUs) required, got ", max_intervals);
+  TORCH_CHECK(data.scalar_type() == at::kByte && data.dim() == 2 && data.size(0) >= 1 && data.size(1) >= 1 &&
+                  data.size(1) <= INT_MAX && data.is_contiguous(),
+              "aiko.jpeg_decode_out: data uint8 [B, cap] contiguous required, 1 <= cap < 2^31");
+  const int64_t B = data.size(0);
+  TORCH_CHECK(B <= 65535, "aiko.jpeg_decode_out: B = ", B, " exceeds the grid limit (65535 frames)");
+  TORCH_CHECK(nbytes.scalar_type() == at::kInt && nbytes.dim() == 1 && nbytes.size(0) == B && nbytes.is_contiguous(),
+              "aiko.jpeg_decode_out: nbytes int32 [B] contiguous required");
+  TORCH_CHECK(desc.scalar_type() == at::kByte && desc.dim() == 2 && (desc.size(0) == B || desc.size(0) == 1) &&
+                  desc.size(1) == 1744 && desc.is_contiguous() && reinterpret_cast<uintptr_t>(desc.data_ptr()) % 4 == 0,
+              "aiko.jpeg_decode_out: desc uint8 [B, 1744] or [1, 1744] contiguous, 4-byte aligned required");
+  TORCH_CHECK(raw.scalar_type() == at::kByte && raw.dim() == 2 && raw.size(0) == B && raw.size(1) == frame &&
+                  raw.is_contiguous(),
+              "aiko.jpeg_decode_out: raw uint8 [B, ", frame, "] contiguous required");
+  TORCH_CHECK(status.scalar_type() == at::kInt && status.dim() == 1 && status.size(0) == B && status.is_contiguous(),
+              "aiko.jpeg_decode_out: status int32 [B] contiguous required");
+  const int64_t need = (4 * B * (1 + 2 * max_intervals) + 15) / 16 * 16 + B * nblocks * 128;
+  TORCH_CHECK(workspace.scalar_type() == at::kByte && workspace.dim() == 1 && workspace.is_contiguous() &&
+                  workspace.numel() >= need && reinterpret_cast<uintptr_t>(workspace.data_ptr()) % 16 == 0,
+              "aiko.jpeg_decode_out: workspace uint8 [>= ", need, "] contiguous, 16-byte aligned required");
+  // no output may overlap an input or another output
+  auto overlap = [](const at::Tensor& x, const at::Tensor& y) {
+    const auto xp = reinterpret_cast<uintptr_t>(x.data_ptr()), yp = reinterpret_cast<uintptr_t>(y.data_ptr());
+    const uintptr_t xn = x.numel() * x.element_size(), yn = y.numel() * y.element_size();
+    return xn > 0 && yn > 0 && xp < yp + yn && yp < xp + xn;
+  };
+  for (int o = 3; o < 6; ++o)
+    for (int p = 0; p < o; ++p)
+      TORCH_CHECK(!overlap(*ts[o], *ts[p]), "aiko.jpeg_decode_out: ", names[o], " and ", names[p], " overlap");
+  check_launch(aiko_jpeg_decode(data.data_ptr(), nbytes.data_ptr<int>(), desc.data_ptr(), (int)desc.size(0),
+                                workspace.data_ptr(), raw.data_ptr(), status.data_ptr<int>(), (int)B, (int)H, (int)W,
+                                (int)fmt, (long)data.size(1), (int)max_intervals, cur_stream()),
+               "jpeg_decode");
+}
+
 void avgpool_out(const at::Tensor& x, at::Tensor& y) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -2033,6 +2093,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("track_detections_out(Tensor det, Tensor count, Tensor boxes, Tensor meta, Tensor issued, int k, float iou, int max_age, float min_score, bool class_aware, int label_mod, Tensor(a!) boxes_out, Tensor(b!) meta_out, Tensor(c!) issued_out, Tensor(d!) ids, Tensor(e!) hits, Tensor(f!) labels) -> ()");
   m.def("motion_detect_out(Tensor frames, Tensor bg, Tensor seen, int cell, int threshold, int learn_shift, bool learn_moving, int warmup, int min_cells, Tensor(a!) bg_out, Tensor(b!) seen_out, Tensor(c!) det, Tensor(d!) count, Tensor(e!) mask, Tensor(f!) cells) -> ()");
   m.def("jpeg_encode_out(Tensor raw, int height, int width, int fmt, Tensor tables, int header_len, int seg_cap, Tensor(a!) stream, Tensor(b!) nbytes, Tensor(c!) workspace) -> ()");
+  m.def("jpeg_decode_out(Tensor data, Tensor nbytes, Tensor desc, int height, int width, int fmt, int max_intervals, Tensor(a!) raw, Tensor(b!) status, Tensor(c!) workspace) -> ()");
   m.def("resample_out(Tensor pcm, Tensor hist, Tensor filt, int L, int M, Tensor(a!) out, Tensor(b!) hist_out) -> ()");
   m.def("zero_border_rows_(Tensor(a!) x, int rows) -> ()");
   m.def("sppf_pool_(Tensor(a!) cat, int c, int k) -> ()");
@@ -2082,6 +2143,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("track_detections_out", &track_detections_out);
   m.impl("motion_detect_out", &motion_detect_out);
   m.impl("jpeg_encode_out", &jpeg_encode_out);
+  m.impl("jpeg_decode_out", &jpeg_decode_out);
   m.impl("zero_border_rows_", &zero_border_rows_);
   m.impl("sppf_pool_", &sppf_pool_);
   m.impl("stem_pool_out", &stem_pool_out);

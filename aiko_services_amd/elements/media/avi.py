@@ -132,21 +132,32 @@ def _decode(buf: bytes, cid: bytes, info: dict) -> np.ndarray:
         if info["bottom_up"]:
             a = a[::-1]
         return np.ascontiguousarray(a)
-    if comp.upper() in (b"MJPG", b"JPEG", b"AVRN", b"LJPG", b"DMB1"):
+    if comp.upper() in _JPEG_CODECS:
         from PIL import Image
         return np.asarray(Image.open(io.BytesIO(buf)).convert("RGB"))
     raise ValueError(f"AVI codec {comp!r} needs OpenCV (supported here: MJPG, uncompressed)")
 
 
-def iter_avi(path):
-    """RGB uint8 frames [H, W, 3] of an AVI file's first video stream."""
+_JPEG_CODECS = (b"MJPG", b"JPEG", b"AVRN", b"LJPG", b"DMB1")
+
+
+def iter_avi(path, raw=False):
+    """RGB uint8 frames [H, W, 3] of an AVI file's first video stream.  ``raw=True`` (Motion-JPEG
+    only): the chunks as they are, 1-D uint8 arrays, each one coded frame for ``JpegDecode``; an
+    uncompressed video is a ``ValueError``."""
     info, frames = _parse(path)
+    if raw and (info["compression"].upper() not in _JPEG_CODECS or any(cid[2:] == b"db" for _, _, cid in frames)):
+        raise ValueError(f"{path}: raw frames need a Motion-JPEG video, this one is "
+                         f"{'uncompressed' if info['compression'] == bytes(4) else repr(info['compression'])}")
     with open(path, "rb") as f:
         for off, size, cid in frames:
             if size == 0:                           # dropped-frame marker: repeat nothing
                 continue
             f.seek(off)
-            yield _decode(f.read(size), cid, info)
+            if raw:
+                yield np.frombuffer(f.read(size), np.uint8)
+            else:
+                yield _decode(f.read(size), cid, info)
 
 
 def read_avi(path) -> np.ndarray:

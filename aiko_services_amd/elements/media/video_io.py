@@ -157,9 +157,13 @@ def write_y4m(path, frames, fps=30):
 
 def iter_video_frames(path, raw=False):
     """RGB uint8 frames of a video file / frame directory, whatever backend is available.
-    ``raw=True`` (Y4M only): each frame's packed planes as a 1-D uint8 array, unconverted."""
+    ``raw=True``: each frame as a 1-D uint8 array, unconverted: a Y4M file's packed planes, or the
+    coded frames of a Motion-JPEG ``.avi`` (for ``JpegDecode``)."""
     path = Path(path)
     if raw:
+        if not path.is_dir() and path.suffix.lower() == ".avi":
+            yield from iter_avi(path, raw=True)
+            return
         if path.is_dir() or path.suffix.lower() != ".y4m":
             raise ValueError(f"{path}: raw frames need a .y4m file")
         for _fmt, _h, _w, packed in iter_y4m(path, raw=True):
@@ -215,8 +219,9 @@ class VideoOutput(PipelineElement):
 
 
 class VideoReadFile(DataSource):
-    """Parameter ``raw: true`` (Y4M files only): ``images`` are the frames' packed planes, 1-D uint8
-    arrays, for a ``FrameUpload`` with ``format`` i420 / i444; any other file is an error."""
+    """Parameter ``raw: true``: for a Y4M file ``images`` are the frames' packed planes, 1-D uint8
+    arrays, for a ``FrameUpload`` with ``format`` i420 / i444; for a Motion-JPEG ``.avi`` they are the
+    coded frames as they lie in the file, for a ``JpegDecode``; any other file is an error."""
 
     def __init__(self, context):
         context.set_protocol("video_read_file:0")

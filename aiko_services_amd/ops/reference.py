@@ -742,3 +742,166 @@ def jpeg_encode_ref(raw: torch.Tensor, height: int, width: int, fmt: str = "i420
             nbytes[b] = len(out)
             stream[b, :len(out)] = torch.frombuffer(out, dtype=torch.uint8)
     return stream, nbytes
+
+
+class _JpegError(Exception):
+    """A status bit of ``ops.jpeg_decode``, raised where an interval stops."""
+
+
+def _jpeg_interval_ref(d: bytes, start: int, end: int, tables, layout, mcus, coef) -> int:
+    """The blocks of the MCUs ``mcus`` from ``d[start:end]`` into ``coef [blocks, 64]`` (zigzag order), bit by
+    bit on demand; the interval's status bits.  ``tables[comp]``: ``(dc, ac)``, each ``(maxcode, valoff,
+    symbols)``; ``layout``: the component of every block of an MCU."""
+    pos, cur, left = start, 0, 0
+
+    def bit() -> int:
+        nonlocal pos, cur, left
+        if not left:
+            if pos >= end:
+                raise _JpegError(4)
+            cur = d[pos]
+            if cur != 0xFF:
+                pos += 1
+            elif pos + 1 < end and d[pos + 1] == 0:
+                pos += 2
+            else:
+                raise _JpegError(16)
+            left = 8
+        left -= 1
+        return cur >> left & 1
+
+    def symbol(table) -> int:
+        maxcode, valoff, symbols = table
+        code = 0
+        for length in range(16):
+            code = code << 1 | bit()
+            if code <= maxcode[length]:
+                return symbols[(code + valoff[length]) & 255]
+        raise _JpegError(2)
+
+    def value(size: int) -> int:
+        v = 0
+        for _ in range(size):
+            v = v << 1 | bit()
+        return v if v >= 1 << (size - 1) else v - (1 << size) + 1
+
+    pred = [0, 0, 0]
+    try:
+        for mcu in mcus:
+            for sub, comp in enumerate(layout):
+                out = coef[mcu * len(layout) + sub]
+                dc, ac = tables[comp]
+                size = symbol(dc) & 15
+                pred[comp] = min(max(pred[comp] + (value(size) if size else 0), -32768), 32767)
+                out[0] = pred[comp]
+                k = 1
+                while k < 64:
+                    rs = symbol(ac)
+                    run, size = rs >> 4, rs & 15
+                    if size == 0:
+                        if run != 15:
+                            break                           # EOB
+                        if k + 16 > 64:
+                            raise _JpegError(8)
+                        k += 16
+                        continue
+                    k += run
+                    if k > 63:
+                        raise _JpegError(8)
+                    out[k] = value(size)
+                    k += 1
+    except _JpegError as exc:
+        return exc.args[0]
+    return 0
+
+
+def jpeg_decode_ref(data: torch.Tensor, nbytes: torch.Tensor, desc: torch.Tensor, height: int, width: int,
+                    fmt: str = "i420", *, restart_interval: int | None = None, coefficients: list | None = None):
+    """``ops.jpeg_decode.jpeg_decode`` on the CPU in plain loops, the rule of
+    :mod:`~aiko_services_amd.ops.jpeg_decode` literally, from the same tensors: ``data`` uint8 ``[B, cap]``,
+    ``nbytes`` int32 ``[B]``, ``desc`` uint8 ``[B | 1, PLAN_BYTES]`` -> ``(raw uint8 [B, frame_bytes], status
+    int32 [B])``.  What the rule leaves unspecified is fixed here: a frame whose marker scan fails is all
+    zero bytes, an interval that stops at an error leaves the rest of its coefficients zero.
+    ``coefficients`` (a list) receives per frame the int16 ``[blocks, 64]`` coefficients in zigzag order."""
+    import struct
+
+    import numpy as np
+
+    from . import jpeg as J
+    from . import jpeg_decode as D
+    from .yuv import frame_bytes
+    mh, mw, per, my, mx = D.geometry(fmt, height, width)
+    H, W = int(height), int(width)
+    max_int = D.intervals(fmt, H, W, restart_interval)
+    data, nbytes, desc = data.cpu(), nbytes.cpu(), desc.cpu()
+    B, cap = data.shape
+    if desc.dim() != 2 or desc.shape[0] not in (1, B) or desc.shape[1] != D.PLAN_BYTES:
+        raise ValueError(f"jpeg_decode_ref: desc [{B} | 1, {D.PLAN_BYTES}] required, got {tuple(desc.shape)}")
+    mcus = my * mx
+    layout = {"i420": (0, 0, 0, 0, 1, 2), "yuyv": (0, 0, 1, 2), "i444": (0, 1, 2)}[fmt]
+    # (block row, block column) of an MCU's blocks inside the MCU, and the component's blocks per MCU side
+    place = {"i420": ((0, 0), (0, 1), (1, 0), (1, 1), (0, 0), (0, 0)), "yuyv": ((0, 0), (0, 1), (0, 0), (0, 0)),
+             "i444": ((0, 0),) * 3}[fmt]
+    span = {"i420": (2, 2), "yuyv": (1, 2), "i444": (1, 1)}[fmt]       # luma blocks per MCU: rows, columns
+    M = np.array(J.DCT_MATRIX, dtype=np.int64)
+    unzig = np.empty(64, dtype=np.int64)
+    unzig[list(J.ZIGZAG)] = np.arange(64)                               # natural index -> zigzag position
+    ch, cw = ((H + 1) // 2, (W + 1) // 2) if fmt == "i420" else ((H, W // 2) if fmt == "yuyv" else (H, W))
+    raw = torch.zeros(B, frame_bytes(fmt, H, W), dtype=torch.uint8)
+    status = torch.zeros(B, dtype=torch.int32)
+    for b in range(B):
+        plan = bytes(desc[b if desc.shape[0] > 1 else 0].tolist())
+        scan, dri = struct.unpack_from("<ii", plan, 0)
+        sel = plan[8:14]
+        quant = [np.array(list(plan[16 + 64 * c:80 + 64 * c]), dtype=np.int64) for c in range(3)]
+        huff = []
+        for slot in range(4):
+            at = 208 + 384 * slot
+            huff.append((struct.unpack_from("<16i", plan, at), struct.unpack_from("<16i", plan, at + 64),
+                         plan[at + 128:at + 384]))
+        tables = [(huff[sel[c] & 1], huff[2 + (sel[3 + c] & 1)]) for c in range(3)]
+        coef = np.zeros((mcus * per, 64), dtype=np.int64)
+        n = int(nbytes[b])
+        nint = -(-mcus // dri) if dri > 0 else 1
+        if n < 1 or n > cap or scan < 2 or scan > n - 2 or dri < 0 or nint > max_int:
+            st = 1
+        else:
+            d = bytes(data[b, :n].tolist())
+            st = 0 if d[n - 2:] == b"\xff\xd9" else 1
+            marks = [i for i in range(scan, n - 3) if d[i] == 0xFF and 0xD0 <= d[i + 1] <= 0xD7]
+            if len(marks) != nint - 1 or any(d[i + 1] & 7 != k & 7 for k, i in enumerate(marks)):
+                st = 1
+            if st == 0:
+                starts = [scan] + [i + 2 for i in marks]
+                ends = marks + [n - 2]
+                for i in range(nint):
+                    span_mcus = range(i * dri, min((i + 1) * dri, mcus)) if dri > 0 else range(mcus)
+                    st |= _jpeg_interval_ref(d, starts[i], ends[i], tables, layout, span_mcus, coef)
+        status[b] = st
+        if coefficients is not None:
+            coefficients.append(torch.from_numpy(coef.astype(np.int16)))
+        if st & 1:
+            continue
+        planes = [np.zeros((H, W), np.uint8), np.zeros((ch, cw), np.uint8), np.zeros((ch, cw), np.uint8)]
+        for k in range(mcus * per):
+            mcu, sub = divmod(k, per)
+            comp = layout[sub]
+            rows, cols = span if comp == 0 else (1, 1)
+            by = (mcu // mx) * rows + place[sub][0]
+            bx = (mcu % mx) * cols + place[sub][1]
+            c = np.clip(coef[k][unzig] * quant[comp], -2048, 2047).reshape(8, 8)
+            t = (M.T @ c + 1024) >> 11                      # columns; >> on int64 is arithmetic
+            x = (t @ M + 16384) >> 15                       # rows
+            s = np.clip(x + 128, 0, 255).astype(np.uint8)
+            plane = planes[comp]
+            hh, ww = min(8, plane.shape[0] - 8 * by), min(8, plane.shape[1] - 8 * bx)
+            if hh > 0 and ww > 0:
+                plane[8 * by:8 * by + hh, 8 * bx:8 * bx + ww] = s[:hh, :ww]
+        if fmt == "yuyv":
+            packed = np.empty((H, W // 2, 4), np.uint8)
+            packed[:, :, 0], packed[:, :, 2] = planes[0][:, 0::2], planes[0][:, 1::2]
+            packed[:, :, 1], packed[:, :, 3] = planes[1], planes[2]
+            raw[b] = torch.from_numpy(packed.reshape(-1))
+        else:
+            raw[b] = torch.from_numpy(np.concatenate([p.reshape(-1) for p in planes]))
+    return raw, status
