@@ -77,6 +77,10 @@ int aiko_track_detections(const float* det, const int* count, const float* boxes
 int aiko_motion_detect(const void* frames, const int* bg, const int* seen, int* bg_out, int* seen_out, float* det,
                        int* count, void* mask, int* cells, int B, int H, int W, int cell, int threshold,
                        int learn_shift, int learn_moving, int warmup, int min_cells, int max_det, hipStream_t stream);
+int aiko_voice_activity(const float* audio, const int* state, int* state_out, int* level, int* zc, void* mask, int* seg,
+                        int* count, int* speech, int* silent, int B, int F, int frame, int threshold, int min_level,
+                        int up_shift, int speech_shift, int down_shift, int warmup, int attack, int hang, int max_zc,
+                        int window, int max_seg, hipStream_t stream);
 int aiko_jpeg_encode(const void* raw, const void* tables, int header_len, void* workspace, void* stream, int* nbytes,
                      int B, int H, int W, int fmt, long cap, int seg_cap, hipStream_t stream_);
 int aiko_jpeg_decode(const void* data, const int* nbytes, const void* desc, int desc_rows, void* workspace, void* raw,
@@ -1518,6 +1522,85 @@ void motion_detect_out(const at::Tensor& frames, const at::Tensor& bg, const at:
                "motion_detect");
 }
 
+// One voice-activity step (vad_ops.hip; the rule is in ops/vad.py): audio fp32 [B, n] at 16 kHz and the
+// state [B, 8] -> the next state in state_out, per frame of ``frame`` samples level / zc / mask [B, F],
+// the runs of the mask in seg [B, max_seg, 2] / count [B], the speech frames in speech [B] and
+// silent [B].  Two launches on the current stream
+void voice_activity_out(const at::Tensor& audio, const at::Tensor& state, int64_t frame, int64_t threshold,
+                        int64_t min_level, int64_t up_shift, int64_t speech_shift, int64_t down_shift, int64_t warmup,
+                        int64_t attack, int64_t hang, int64_t max_zc, int64_t window, at::Tensor& state_out,
+                        at::Tensor& level, at::Tensor& zc, at::Tensor& mask, at::Tensor& seg, at::Tensor& count,
+                        at::Tensor& speech, at::Tensor& silent) {
+  const at::Tensor* ins[2] = {&audio, &state};
+  const char* in_names[2] = {"audio", "state"};
+  const at::Tensor* outs[8] = {&state_out, &level, &zc, &mask, &seg, &count, &speech, &silent};
+  const char* out_names[8] = {"state_out", "level", "zc", "mask", "seg", "count", "speech", "silent"};
+  for (int i = 0; i < 2; ++i) check_cuda(*ins[i], in_names[i]);
+  for (int o = 0; o < 8; ++o) check_cuda(*outs[o], out_names[o]);
+  TORCH_CHECK(state.device() == audio.device(), "aiko.voice_activity_out: tensors on different devices");
+  for (int o = 0; o < 8; ++o)
+    TORCH_CHECK(outs[o]->device() == audio.device(), "aiko.voice_activity_out: tensors on different devices");
+  TORCH_CHECK(audio.scalar_type() == at::kFloat && audio.dim() == 2 && audio.is_contiguous() && audio.size(0) >= 1,
+              "aiko.voice_activity_out: audio fp32 [B, n] contiguous required");
+  TORCH_CHECK(frame == 160 || frame == 320 || frame == 480,
+              "aiko.voice_activity_out: frame in {160, 320, 480} required, got ", frame);
+  const int64_t B = audio.size(0), n = audio.size(1);
+  TORCH_CHECK(n >= frame && n % frame == 0, "aiko.voice_activity_out: n % frame != 0 or n = 0 (n = ", n,
+              ", frame = ", frame, "): a chunk is whole frames");
+  const int64_t F = n / frame;
+  TORCH_CHECK(F <= 4096, "aiko.voice_activity_out: F = ", F, " frames exceed 4096 per call");
+  TORCH_CHECK(B <= 65535, "aiko.voice_activity_out: B = ", B, " exceeds the grid limit (65535 streams)");
+  const struct { const char* name; int64_t v, lo, hi; } ranges[] = {
+      {"threshold", threshold, 0, 1023}, {"min_level", min_level, 0, 1023}, {"up_shift", up_shift, 0, 16},
+      {"speech_shift", speech_shift, 0, 16}, {"down_shift", down_shift, 0, 16}, {"warmup", warmup, 1, INT_MAX},
+      {"attack", attack, 1, INT_MAX}, {"hang", hang, 0, INT_MAX}, {"max_zc", max_zc, 0, 479},
+      {"window", window, 1, INT_MAX}};
+  for (const auto& r : ranges)
+    TORCH_CHECK(r.v >= r.lo && r.v <= r.hi, "aiko.voice_activity_out: ", r.lo, " <= ", r.name, " <= ", r.hi,
+                " required, got ", r.v);
+  auto is_state = [&](const at::Tensor& s) {
+    return s.scalar_type() == at::kInt && s.dim() == 2 && s.size(0) == B && s.size(1) == 8 && s.is_contiguous();
+  };
+  TORCH_CHECK(is_state(state), "aiko.voice_activity_out: state int32 [B, 8] contiguous required, B = ", B);
+  TORCH_CHECK(is_state(state_out), "aiko.voice_activity_out: state_out int32 [B, 8] contiguous required, B = ", B);
+  for (const at::Tensor* t : {&level, &zc})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 2 && t->size(0) == B && t->size(1) == F &&
+                    t->is_contiguous(),
+                "aiko.voice_activity_out: level and zc int32 [B, F] = [", B, ", ", F, "] contiguous required");
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.dim() == 2 && mask.size(0) == B && mask.size(1) == F &&
+                  mask.is_contiguous(),
+              "aiko.voice_activity_out: mask uint8 [B, F] = [", B, ", ", F, "] contiguous required");
+  TORCH_CHECK(seg.scalar_type() == at::kInt && seg.dim() == 3 && seg.size(0) == B && seg.size(2) == 2 &&
+                  seg.is_contiguous(),
+              "aiko.voice_activity_out: seg int32 [B, max_seg, 2] contiguous required");
+  const int64_t max_seg = seg.size(1);
+  TORCH_CHECK(max_seg >= 1 && max_seg <= 64, "aiko.voice_activity_out: 1 <= max_seg <= 64 required, got ", max_seg);
+  for (const at::Tensor* t : {&count, &speech, &silent})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1 && t->size(0) == B && t->is_contiguous(),
+                "aiko.voice_activity_out: count, speech and silent int32 [B] contiguous required");
+  // no output may overlap an input or another output
+  auto overlap = [](const at::Tensor& x, const at::Tensor& y) {
+    const auto xp = reinterpret_cast<uintptr_t>(x.data_ptr()), yp = reinterpret_cast<uintptr_t>(y.data_ptr());
+    const uintptr_t xn = x.numel() * x.element_size(), yn = y.numel() * y.element_size();
+    return xn > 0 && yn > 0 && xp < yp + yn && yp < xp + xn;
+  };
+  for (int o = 0; o < 8; ++o) {
+    for (int i = 0; i < 2; ++i)
+      TORCH_CHECK(!overlap(*outs[o], *ins[i]), "aiko.voice_activity_out: ", out_names[o], " and ", in_names[i],
+                  " overlap");
+    for (int p = 0; p < o; ++p)
+      TORCH_CHECK(!overlap(*outs[o], *outs[p]), "aiko.voice_activity_out: ", out_names[o], " and ", out_names[p],
+                  " overlap");
+  }
+  check_launch(aiko_voice_activity(audio.data_ptr<float>(), state.data_ptr<int>(), state_out.data_ptr<int>(),
+                                   level.data_ptr<int>(), zc.data_ptr<int>(), mask.data_ptr(), seg.data_ptr<int>(),
+                                   count.data_ptr<int>(), speech.data_ptr<int>(), silent.data_ptr<int>(), (int)B, (int)F,
+                                   (int)frame, (int)threshold, (int)min_level, (int)up_shift, (int)speech_shift,
+                                   (int)down_shift, (int)warmup, (int)attack, (int)hang, (int)max_zc, (int)window,
+                                   (int)max_seg, cur_stream()),
+               "voice_activity");
+}
+
 // Baseline JPEG (jpeg_ops.hip; the rule is in ops/jpeg.py): raw planar frames [B, frame_bytes] (fmt 1: i420,
 // 2: i444) -> one JFIF stream per frame in stream [B, cap], its length (-1: overflow) in nbytes [B].  tables is
 // ops.jpeg.device_tables' tensor (864 words, then header_len bytes of header); workspace holds an int32 and
@@ -2092,6 +2175,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("window_shift_out(Tensor src, Tensor chunk, Tensor(a!) dst) -> ()");
   m.def("track_detections_out(Tensor det, Tensor count, Tensor boxes, Tensor meta, Tensor issued, int k, float iou, int max_age, float min_score, bool class_aware, int label_mod, Tensor(a!) boxes_out, Tensor(b!) meta_out, Tensor(c!) issued_out, Tensor(d!) ids, Tensor(e!) hits, Tensor(f!) labels) -> ()");
   m.def("motion_detect_out(Tensor frames, Tensor bg, Tensor seen, int cell, int threshold, int learn_shift, bool learn_moving, int warmup, int min_cells, Tensor(a!) bg_out, Tensor(b!) seen_out, Tensor(c!) det, Tensor(d!) count, Tensor(e!) mask, Tensor(f!) cells) -> ()");
+  m.def("voice_activity_out(Tensor audio, Tensor state, int frame, int threshold, int min_level, int up_shift, int speech_shift, int down_shift, int warmup, int attack, int hang, int max_zc, int window, Tensor(a!) state_out, Tensor(b!) level, Tensor(c!) zc, Tensor(d!) mask, Tensor(e!) seg, Tensor(f!) count, Tensor(g!) speech, Tensor(h!) silent) -> ()");
   m.def("jpeg_encode_out(Tensor raw, int height, int width, int fmt, Tensor tables, int header_len, int seg_cap, Tensor(a!) stream, Tensor(b!) nbytes, Tensor(c!) workspace) -> ()");
   m.def("jpeg_decode_out(Tensor data, Tensor nbytes, Tensor desc, int height, int width, int fmt, int max_intervals, Tensor(a!) raw, Tensor(b!) status, Tensor(c!) workspace) -> ()");
   m.def("resample_out(Tensor pcm, Tensor hist, Tensor filt, int L, int M, Tensor(a!) out, Tensor(b!) hist_out) -> ()");
@@ -2142,6 +2226,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("resample_out", &resample_out);
   m.impl("track_detections_out", &track_detections_out);
   m.impl("motion_detect_out", &motion_detect_out);
+  m.impl("voice_activity_out", &voice_activity_out);
   m.impl("jpeg_encode_out", &jpeg_encode_out);
   m.impl("jpeg_decode_out", &jpeg_decode_out);
   m.impl("zero_border_rows_", &zero_border_rows_);

@@ -16,8 +16,11 @@
 * ``FeatureSink``   — mean-pooled features to pinned host memory as a DeviceResult (the
   encoder-only BASELINE config's consumer);
 * ``WhisperTranscribe`` — greedy text decoding of the features (``models/whisper_decoder.py``),
-  ``{"tokens", "text"}`` like the reference's ``PE_WhisperX`` output;
-* ``SpeechToText``  — ``PE_WhisperX`` in one element: audio -> encoder -> decoder -> text.
+  ``{"tokens", "text"}`` like the reference's ``PE_WhisperX`` output; with ``silent`` from
+  ``VoiceActivity`` (``elements/gpu/vad.py``) a stream in which nobody spoke is done before its first
+  step;
+* ``SpeechToText``  — ``PE_WhisperX`` in one element: audio -> encoder -> decoder -> text
+  (``vad: true``: voice activity first, as WhisperX does).
 """
 from __future__ import annotations
 
@@ -231,7 +234,10 @@ class WhisperTranscribe(GpuPipelineElement):
     (default on: stop once every stream has emitted end-of-text, checked every 8 steps),
     ``defer_text`` (default off: with it the tokens come back as a DeviceResult on pinned host
     memory without a host synchronisation and ``text`` is not produced — for throughput runs
-    where the next frame's encoder should queue behind this frame's decoder)."""
+    where the next frame's encoder should queue behind this frame's decoder).  An optional input
+    ``silent`` (int32 [B] on the device, ``VoiceActivity``'s output) starts those streams as done:
+    their tokens are the prompt and end-of-text, their text "<silence>", and a batch of silent streams
+    ends at the first ``stop_early`` check."""
     lane_safe = True          # one decode state / graph per lane (ws_tag)
 
     def __init__(self, context):
@@ -245,22 +251,22 @@ class WhisperTranscribe(GpuPipelineElement):
         self.load_model_weights(self.model)
         self.tokenizer = _load_tokenizer(self)
 
-    def _decode(self, features, stop: bool):
+    def _decode(self, features, stop: bool, silent=None):
         self.model.ws_tag = f"lane{self.lane}." if self.lane else ""
         return self.model.transcribe(features, max_new_tokens=int(_p(self, "max_tokens", 96)),
-                                     use_graph=self.use_graph, check_every=8 if stop else 0)
+                                     use_graph=self.use_graph, check_every=8 if stop else 0, silent=silent)
 
-    def transcribe(self, features):
+    def transcribe(self, features, silent=None):
         from ...models.whisper_decoder import decode_text
         stop = str(_p(self, "stop_early", True)).lower() in ("true", "1", "yes")
-        tokens = self._decode(features, stop).cpu()
+        tokens = self._decode(features, stop, silent).cpu()
         texts = [_reply(t) for t in decode_text(tokens, self.tokenizer, eot=self.model.eot)]
         return tokens, texts
 
-    def process_frame(self, stream, features, t_submit=None):
+    def process_frame(self, stream, features, t_submit=None, silent=None):
         t0 = t_submit if isinstance(t_submit, float) else None
         if str(_p(self, "defer_text", False)).lower() in ("true", "1", "yes"):
-            tok = self._decode(features, False)
+            tok = self._decode(features, False, silent)
             key = (tuple(tok.shape), self.lane)
             bufs = self.__dict__.setdefault("_pinned", {})
             ring = bufs.get(key)
@@ -276,14 +282,16 @@ class WhisperTranscribe(GpuPipelineElement):
             ev.record()
             slot[1] = ev
             return StreamEvent.OKAY, {"transcript": DeviceResult({"tokens": slot[0]}, ev, t_submit=t0)}
-        tokens, texts = self.transcribe(features)
+        tokens, texts = self.transcribe(features, silent)
         return StreamEvent.OKAY, {"tokens": tokens, "text": texts[0] if len(texts) == 1 else texts,
                                   "transcript": DeviceResult({"tokens": tokens}, None, t_submit=t0)}
 
 
 class SpeechToText(WhisperTranscribe):
     """The reference's ``PE_WhisperX`` shape in one element: ``audio`` (16 kHz samples, [N] or
-    [B, N], host or device) -> log-mel + encoder + greedy decoder -> ``{"text": ...}``."""
+    [B, N], host or device) -> log-mel + encoder + greedy decoder -> ``{"text": ...}``.  ``vad: true``
+    (default off) asks ``ops.vad.voice_activity`` first, as WhisperX asks its detector: a clip without a
+    speech frame is "<silence>" whatever the decoder would have made of it."""
 
     def __init__(self, context):
         super().__init__(context)
@@ -293,6 +301,21 @@ class SpeechToText(WhisperTranscribe):
         path, found = self.get_parameter("encoder_weights")
         if found and path:
             self.encoder.load(str(path))
+        self.vad = str(_p(self, "vad", False)).lower() in ("true", "1", "yes")
+
+    def _silent(self, x):
+        """``vad: true``: one stateless voice-activity call over the clip from the empty state, with
+        ``window`` the clip: ``silent`` [B] on the device, 1 where no frame of a stream is speech.  The
+        clip is cut to whole frames of 20 ms; one longer than the operator's 4096 frames (82 s) goes
+        through in pieces, the state carried."""
+        from ...ops import vad as V
+        frame = V.DEFAULTS["frame"]
+        F = x.shape[1] // frame
+        state, silent = V.new_state(x.shape[0], x.device), None
+        for f0 in range(0, F, V.MAX_FRAMES):
+            piece = x[:, f0 * frame:min(f0 + V.MAX_FRAMES, F) * frame].contiguous()
+            silent, state = V.voice_activity(piece, state, window=F)[4::3]
+        return silent
 
     def process_frame(self, stream, audio):
         x = audio if isinstance(audio, torch.Tensor) else torch.as_tensor(np.asarray(audio, dtype=np.float32))
@@ -302,7 +325,8 @@ class SpeechToText(WhisperTranscribe):
         n = x.shape[1] - x.shape[1] % 320                     # whole encoder frames (320 samples)
         if n <= 0:
             return StreamEvent.OKAY, {"text": "<silence>", "tokens": None}
-        tokens, texts = self.transcribe(self.encoder.encode(x[:, :n].contiguous()))
+        clip = x[:, :n].contiguous()
+        tokens, texts = self.transcribe(self.encoder.encode(clip), self._silent(clip) if self.vad else None)
         return StreamEvent.OKAY, {"tokens": tokens, "text": texts[0] if len(texts) == 1 else texts}
 
 

@@ -279,12 +279,19 @@ class WhisperDecoder(WeightsMixin):
         g.replay()
 
     def transcribe(self, features: torch.Tensor, max_new_tokens: int = 96, use_graph: bool = True,
-                   check_every: int = 8) -> torch.Tensor:
+                   check_every: int = 8, silent=None) -> torch.Tensor:
         """Greedy decoding after the prompt; returns int32 [B, n] on the device (prompt first,
-        ``eot`` after each sequence's end)."""
+        ``eot`` after each sequence's end).  ``silent`` ([B], non-zero: nobody spoke, as
+        ``ops.vad.voice_activity`` reports it) starts those sequences as done: their tokens are the
+        prompt, then ``eot``.  A device tensor is taken without a host copy."""
         self.prepare(features)
         B = features.shape[0]
         st = self._state(B)
+        if silent is not None:
+            silent = torch.as_tensor(silent)
+            if silent.shape != (B,):
+                raise ValueError(f"silent [B = {B}] required, got {tuple(silent.shape)}")
+            st["done"].copy_(silent != 0)
         st["forced"].copy_(torch.tensor(self.prompt, dtype=torch.int32))
         n_steps = min(len(self.prompt) - 1 + max_new_tokens, self.n_ctx - 1)
         for s in range(n_steps):

@@ -627,6 +627,96 @@ def motion_detect_ref(frames: torch.Tensor, state, *, cell: int = 16, threshold:
             MotionState(torch.from_numpy(bg_out.astype(np.int32)), torch.from_numpy(seen_out.astype(np.int32))))
 
 
+# ---- voice activity ---------------------------------------------------------------------------
+
+def vad_level_ref(E: int) -> int:
+    """Step 3 of the rule of ``ops/vad.py``: the level of a frame of energy ``E`` (a Python int)."""
+    if E == 0:
+        return 0
+    p = E.bit_length() - 1
+    mant = ((E >> (p - 4)) if p >= 4 else (E << (4 - p))) & 15
+    return 16 * (p + 1) + mant
+
+
+def voice_activity_ref(audio: torch.Tensor, state, *, frame: int = 320, threshold: int = 48, min_level: int = 0,
+                       up_shift: int = 6, speech_shift: int = 10, down_shift: int = 1, warmup: int = 10,
+                       attack: int = 3, hang: int = 15, max_zc: int = 479, window: int = 1500, max_seg: int = 16):
+    """The definition of :func:`aiko_services_amd.ops.vad.voice_activity` on the CPU, in plain loops
+    over frames: ``(mask, seg, count, speech, silent, level, zc, state_out)`` for fp32 ``audio`` ``[B,
+    n]`` and a ``VadState``.  The samples are scaled in numpy fp32 and rounded by ``np.rint`` (half to
+    even); a frame's two sums are numpy int64, everything after them a Python int.  ``state`` is not
+    modified."""
+    import numpy as np
+
+    from .vad import MAX_FRAMES, VadState, check_parameters
+    check_parameters(frame, threshold, min_level, up_shift, speech_shift, down_shift, warmup, attack, hang, max_zc,
+                     window, max_seg)
+    x = audio.detach().cpu().numpy()
+    if x.dtype != np.float32 or x.ndim != 2 or x.shape[0] < 1:
+        raise ValueError(f"voice_activity_ref: audio fp32 [B, n] required, got {x.dtype} {x.shape}")
+    B, n = x.shape
+    if n == 0 or n % frame or n // frame > MAX_FRAMES:
+        raise ValueError(f"voice_activity_ref: n = {n} is not 1..{MAX_FRAMES} whole frames of {frame}")
+    F = n // frame
+    with np.errstate(over="ignore", invalid="ignore"):
+        v = x * np.float32(32768.0)
+        q = np.where(np.isnan(v), np.float32(0), np.rint(np.clip(v, np.float32(-32768), np.float32(32767))))
+    q = q.astype(np.int64).reshape(B, F, frame)
+    st = state.v.detach().cpu().numpy().astype(np.int64)
+    cap = 2 ** 30
+    level = np.zeros((B, F), np.int32)
+    zc = np.zeros((B, F), np.int32)
+    mask = np.zeros((B, F), np.uint8)
+    seg = np.zeros((B, max_seg, 2), np.int32)
+    count = np.zeros(B, np.int32)
+    speech = np.zeros(B, np.int32)
+    silent = np.zeros(B, np.int32)
+    out = np.zeros((B, 8), np.int32)
+    for b in range(B):
+        floor, seen, run, quiet, on, since = (int(c) for c in st[b, :6])
+        s = max(seen, 0)
+        if s == 0:
+            run, quiet, on, since = 0, 0, 0, cap
+        else:
+            run, quiet, on, since = min(max(run, 0), cap), max(quiet, 0), int(on != 0), min(max(since, 0), cap)
+        floor = min(max(floor, 0), 1023 << 8)
+        runs = []
+        for f in range(F):
+            qf = q[b, f]
+            E, z = int((qf * qf).sum()), int(((qf[1:] < 0) != (qf[:-1] < 0)).sum())
+            lv = vad_level_ref(E)
+            cur = lv << 8
+            if s == 0:
+                floor = cur
+            raw = s >= warmup and lv >= min_level and cur - floor > (threshold << 8) and z <= max_zc
+            if s > 0:
+                k = down_shift if cur < floor else speech_shift if raw else up_shift
+                floor += (cur - floor + ((1 << (k - 1)) if k else 0)) >> k      # Python's >> floors
+            run = min(run + 1, cap) if raw else 0
+            if not on:
+                if run >= attack:
+                    on, quiet = 1, 0
+            else:
+                quiet = 0 if raw else quiet + 1
+                if quiet > hang:
+                    on, quiet = 0, 0
+            if on and (f == 0 or not mask[b, f - 1]):
+                runs.append([f, f + 1])
+            elif on:
+                runs[-1][1] = f + 1
+            level[b, f], zc[b, f], mask[b, f] = lv, z, on
+            since = 0 if on else min(since + 1, cap)
+            s = min(s + 1, 2 ** 31 - 1)
+        for i, r in enumerate(runs[:max_seg]):
+            seg[b, i] = r
+        count[b] = min(len(runs), max_seg)
+        speech[b] = int(mask[b].sum())
+        silent[b] = 1 if since >= window else 0
+        out[b] = (floor, s, run, quiet, on, since, 0, 0)
+    return (torch.from_numpy(mask), torch.from_numpy(seg), torch.from_numpy(count), torch.from_numpy(speech),
+            torch.from_numpy(silent), torch.from_numpy(level), torch.from_numpy(zc), VadState(torch.from_numpy(out)))
+
+
 # ---- JPEG -------------------------------------------------------------------------------------
 
 def _jpeg_planes_ref(frame: torch.Tensor, fmt: str, H: int, W: int):
