@@ -77,6 +77,9 @@ int aiko_track_detections(const float* det, const int* count, const float* boxes
 int aiko_motion_detect(const void* frames, const int* bg, const int* seen, int* bg_out, int* seen_out, float* det,
                        int* count, void* mask, int* cells, int B, int H, int W, int cell, int threshold,
                        int learn_shift, int learn_moving, int warmup, int min_cells, int max_det, hipStream_t stream);
+int aiko_marker_detect(const void* frames, float* det, int* count, int* corners, int* ids, int* cands, void* mask,
+                       void* work, int B, int H, int W, int N, int cell, int contrast, int min_side, int max_cand,
+                       int max_det, int passes, hipStream_t stream);
 int aiko_voice_activity(const float* audio, const int* state, int* state_out, int* level, int* zc, void* mask, int* seg,
                         int* count, int* speech, int* silent, int B, int F, int frame, int threshold, int min_level,
                         int up_shift, int speech_shift, int down_shift, int warmup, int attack, int hang, int max_zc,
@@ -1522,6 +1525,81 @@ void motion_detect_out(const at::Tensor& frames, const at::Tensor& bg, const at:
                "motion_detect");
 }
 
+// Square markers (marker_ops.hip; the rule is in ops/marker.py): frames [B, H, W, 3] -> the markers as
+// detector rows in det [B, max_det, 6] / count [B], their quads in corners [B, max_det, 4, 2], their ids in
+// ids [B, max_det], the candidates' number in cands [B] and the on cells in mask [B, Gh, Gw]; work int32
+// [>= B (H ceil(W / 32) + ceil(H / 16) ceil(W / 16))] is the workspace.  modules = 7 (original) or 6
+// (payload16).  passes: 7, or the bits of the passes to launch alone (measurements).  Three launches on
+// the current stream
+void marker_detect_out(const at::Tensor& frames, int64_t modules, int64_t cell, int64_t contrast, int64_t min_side,
+                       int64_t max_cand, int64_t passes, at::Tensor& det, at::Tensor& count, at::Tensor& corners,
+                       at::Tensor& ids, at::Tensor& cands, at::Tensor& mask, at::Tensor& work) {
+  const at::Tensor* outs[7] = {&det, &count, &corners, &ids, &cands, &mask, &work};
+  const char* out_names[7] = {"det", "count", "corners", "ids", "cands", "mask", "work"};
+  check_cuda(frames, "frames");
+  for (int o = 0; o < 7; ++o) {
+    check_cuda(*outs[o], out_names[o]);
+    TORCH_CHECK(outs[o]->device() == frames.device(), "aiko.marker_detect_out: tensors on different devices");
+  }
+  TORCH_CHECK(frames.scalar_type() == at::kByte && frames.dim() == 4 && frames.size(3) == 3 &&
+                  frames.is_contiguous() && frames.numel() >= 3,
+              "aiko.marker_detect_out: frames uint8 [B, H, W, 3] contiguous required");
+  const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2);
+  TORCH_CHECK(modules == 6 || modules == 7, "aiko.marker_detect_out: modules 7 (original) or 6 (payload16) required, "
+              "got ", modules);
+  TORCH_CHECK(cell == 4 || cell == 8 || cell == 16, "aiko.marker_detect_out: cell in {4, 8, 16} required, got ", cell);
+  TORCH_CHECK(B <= 65535 && H <= 4096 && W <= 4096, "aiko.marker_detect_out: B = ", B, ", H = ", H, ", W = ", W,
+              " exceed the frame limits (65535 frames, 4096 pixels a side)");
+  const int64_t Gh = (H + cell - 1) / cell, Gw = (W + cell - 1) / cell;
+  TORCH_CHECK((Gh + 2) * (Gw + 2) <= 36864, "aiko.marker_detect_out: a grid of ", Gh, " x ", Gw,
+              " cells exceeds the limit ((Gh + 2) (Gw + 2) <= 36864): choose a larger cell");
+  TORCH_CHECK(contrast >= 1 && contrast <= 255, "aiko.marker_detect_out: 1 <= contrast <= 255 required, got ",
+              contrast);
+  TORCH_CHECK(min_side >= 1 && min_side <= 4096, "aiko.marker_detect_out: 1 <= min_side <= 4096 required, got ",
+              min_side);
+  TORCH_CHECK(max_cand >= 1 && max_cand <= 64, "aiko.marker_detect_out: 1 <= max_cand <= 64 required, got ",
+              max_cand);
+  TORCH_CHECK(passes >= 1 && passes <= 7, "aiko.marker_detect_out: passes in 1..7 required, got ", passes);
+  TORCH_CHECK(det.scalar_type() == at::kFloat && det.dim() == 3 && det.size(0) == B && det.size(2) == 6 &&
+                  det.is_contiguous(),
+              "aiko.marker_detect_out: det fp32 [B, max_det, 6] contiguous required");
+  const int64_t max_det = det.size(1);
+  TORCH_CHECK(max_det >= 1 && max_det <= 64, "aiko.marker_detect_out: 1 <= max_det <= 64 required, got ", max_det);
+  for (const at::Tensor* t : {&count, &cands})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1 && t->size(0) == B && t->is_contiguous(),
+                "aiko.marker_detect_out: count and cands int32 [B] contiguous required");
+  TORCH_CHECK(corners.scalar_type() == at::kInt && corners.dim() == 4 && corners.size(0) == B &&
+                  corners.size(1) == max_det && corners.size(2) == 4 && corners.size(3) == 2 && corners.is_contiguous(),
+              "aiko.marker_detect_out: corners int32 [B, max_det, 4, 2] = [", B, ", ", max_det,
+              ", 4, 2] contiguous required");
+  TORCH_CHECK(ids.scalar_type() == at::kInt && ids.dim() == 2 && ids.size(0) == B && ids.size(1) == max_det &&
+                  ids.is_contiguous(),
+              "aiko.marker_detect_out: ids int32 [B, max_det] = [", B, ", ", max_det, "] contiguous required");
+  TORCH_CHECK(mask.scalar_type() == at::kByte && mask.dim() == 3 && mask.size(0) == B && mask.size(1) == Gh &&
+                  mask.size(2) == Gw && mask.is_contiguous(),
+              "aiko.marker_detect_out: mask uint8 [B, Gh, Gw] = [", B, ", ", Gh, ", ", Gw, "] contiguous required");
+  const int64_t need = B * (H * ((W + 31) / 32) + ((H + 15) / 16) * ((W + 15) / 16));
+  TORCH_CHECK(work.scalar_type() == at::kInt && work.dim() == 1 && work.size(0) >= need && work.is_contiguous(),
+              "aiko.marker_detect_out: work int32 [>= ", need, "] contiguous required");
+  // no output may overlap the frames or another output
+  auto overlap = [](const at::Tensor& x, const at::Tensor& y) {
+    const auto xp = reinterpret_cast<uintptr_t>(x.data_ptr()), yp = reinterpret_cast<uintptr_t>(y.data_ptr());
+    const uintptr_t xn = x.numel() * x.element_size(), yn = y.numel() * y.element_size();
+    return xn > 0 && yn > 0 && xp < yp + yn && yp < xp + xn;
+  };
+  for (int o = 0; o < 7; ++o) {
+    TORCH_CHECK(!overlap(*outs[o], frames), "aiko.marker_detect_out: ", out_names[o], " and frames overlap");
+    for (int p = 0; p < o; ++p)
+      TORCH_CHECK(!overlap(*outs[o], *outs[p]), "aiko.marker_detect_out: ", out_names[o], " and ", out_names[p],
+                  " overlap");
+  }
+  check_launch(aiko_marker_detect(frames.data_ptr(), det.data_ptr<float>(), count.data_ptr<int>(),
+                                  corners.data_ptr<int>(), ids.data_ptr<int>(), cands.data_ptr<int>(), mask.data_ptr(),
+                                  work.data_ptr(), (int)B, (int)H, (int)W, (int)modules, (int)cell, (int)contrast,
+                                  (int)min_side, (int)max_cand, (int)max_det, (int)passes, cur_stream()),
+               "marker_detect");
+}
+
 // One voice-activity step (vad_ops.hip; the rule is in ops/vad.py): audio fp32 [B, n] at 16 kHz and the
 // state [B, 8] -> the next state in state_out, per frame of ``frame`` samples level / zc / mask [B, F],
 // the runs of the mask in seg [B, max_seg, 2] / count [B], the speech frames in speech [B] and
@@ -2174,6 +2252,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("mean_rows_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("window_shift_out(Tensor src, Tensor chunk, Tensor(a!) dst) -> ()");
   m.def("track_detections_out(Tensor det, Tensor count, Tensor boxes, Tensor meta, Tensor issued, int k, float iou, int max_age, float min_score, bool class_aware, int label_mod, Tensor(a!) boxes_out, Tensor(b!) meta_out, Tensor(c!) issued_out, Tensor(d!) ids, Tensor(e!) hits, Tensor(f!) labels) -> ()");
+  m.def("marker_detect_out(Tensor frames, int modules, int cell, int contrast, int min_side, int max_cand, int passes, Tensor(a!) det, Tensor(b!) count, Tensor(c!) corners, Tensor(d!) ids, Tensor(e!) cands, Tensor(f!) mask, Tensor(g!) work) -> ()");
   m.def("motion_detect_out(Tensor frames, Tensor bg, Tensor seen, int cell, int threshold, int learn_shift, bool learn_moving, int warmup, int min_cells, Tensor(a!) bg_out, Tensor(b!) seen_out, Tensor(c!) det, Tensor(d!) count, Tensor(e!) mask, Tensor(f!) cells) -> ()");
   m.def("voice_activity_out(Tensor audio, Tensor state, int frame, int threshold, int min_level, int up_shift, int speech_shift, int down_shift, int warmup, int attack, int hang, int max_zc, int window, Tensor(a!) state_out, Tensor(b!) level, Tensor(c!) zc, Tensor(d!) mask, Tensor(e!) seg, Tensor(f!) count, Tensor(g!) speech, Tensor(h!) silent) -> ()");
   m.def("jpeg_encode_out(Tensor raw, int height, int width, int fmt, Tensor tables, int header_len, int seg_cap, Tensor(a!) stream, Tensor(b!) nbytes, Tensor(c!) workspace) -> ()");
@@ -2225,6 +2304,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("window_shift_out", &window_shift_out);
   m.impl("resample_out", &resample_out);
   m.impl("track_detections_out", &track_detections_out);
+  m.impl("marker_detect_out", &marker_detect_out);
   m.impl("motion_detect_out", &motion_detect_out);
   m.impl("voice_activity_out", &voice_activity_out);
   m.impl("jpeg_encode_out", &jpeg_encode_out);

@@ -3,3 +3,4 @@ ResNet-50, top-k."""
 from .audio_ingest import AudioResample  # noqa: F401
 from .egress import FrameDownload, RgbToYuv  # noqa: F401
 from .ingest import YuvToRgb  # noqa: F401
+from .marker import MarkerDetector, MarkerResults  # noqa: F401
