@@ -84,6 +84,13 @@ int aiko_voice_activity(const float* audio, const int* state, int* state_out, in
                         int* count, int* speech, int* silent, int B, int F, int frame, int threshold, int min_level,
                         int up_shift, int speech_shift, int down_shift, int warmup, int attack, int hang, int max_zc,
                         int window, int max_seg, hipStream_t stream);
+int aiko_spectrum(const float* audio, const float* window, const float* twiddle, const int* band_start, float* power,
+                  float* amplitudes, float* band_amplitudes, int* peak_bins, float* peak_amplitudes, int* peak_counts,
+                  int B, long n, int F, int n_fft, int hop, int bands, int max_peaks, float inv_F, float lo, float hi,
+                  int k_lo, int k_hi, int local, hipStream_t stream);
+int aiko_spectrum_graph(const int* peak_bins, const float* peak_amplitudes, const int* peak_counts, const int* bin_px,
+                        void* image, int B, int H, int W, int K, int max_peaks, double y_max, int r, int g, int b,
+                        hipStream_t stream);
 int aiko_jpeg_encode(const void* raw, const void* tables, int header_len, void* workspace, void* stream, int* nbytes,
                      int B, int H, int W, int fmt, long cap, int seg_cap, hipStream_t stream_);
 int aiko_jpeg_decode(const void* data, const int* nbytes, const void* desc, int desc_rows, void* workspace, void* raw,
@@ -1679,6 +1686,141 @@ void voice_activity_out(const at::Tensor& audio, const at::Tensor& state, int64_
                "voice_activity");
 }
 
+// One spectrum step (spectrum_ops.hip; the rule is in ops/spectrum.py): audio fp32 [B, n] and the host tables
+// window [n_fft], twiddle [n_fft / 2, 2], band_start [bands + 1] -> power [B, F, K], amplitudes [B, K],
+// band_amplitudes [B, bands], peak_bins / peak_amplitudes [B, max_peaks], peak_counts [B].  inv_F, lo and hi are
+// fp32 values.  Two launches on the current stream
+void spectrum_out(const at::Tensor& audio, const at::Tensor& window, const at::Tensor& twiddle,
+                  const at::Tensor& band_start, int64_t n_fft, int64_t hop, double inv_F, double lo, double hi,
+                  int64_t k_lo, int64_t k_hi, bool local, at::Tensor& power, at::Tensor& amplitudes,
+                  at::Tensor& band_amplitudes, at::Tensor& peak_bins, at::Tensor& peak_amplitudes,
+                  at::Tensor& peak_counts) {
+  const at::Tensor* ins[4] = {&audio, &window, &twiddle, &band_start};
+  const char* in_names[4] = {"audio", "window", "twiddle", "band_start"};
+  const at::Tensor* outs[6] = {&power, &amplitudes, &band_amplitudes, &peak_bins, &peak_amplitudes, &peak_counts};
+  const char* out_names[6] = {"power", "amplitudes", "band_amplitudes", "peak_bins", "peak_amplitudes", "peak_counts"};
+  for (int i = 0; i < 4; ++i) check_cuda(*ins[i], in_names[i]);
+  for (int o = 0; o < 6; ++o) check_cuda(*outs[o], out_names[o]);
+  for (int i = 1; i < 4; ++i)
+    TORCH_CHECK(ins[i]->device() == audio.device(), "aiko.spectrum_out: tensors on different devices");
+  for (int o = 0; o < 6; ++o)
+    TORCH_CHECK(outs[o]->device() == audio.device(), "aiko.spectrum_out: tensors on different devices");
+  TORCH_CHECK(audio.scalar_type() == at::kFloat && audio.dim() == 2 && audio.is_contiguous() && audio.size(0) >= 1 &&
+                  audio.size(1) >= 1,
+              "aiko.spectrum_out: audio fp32 [B, n >= 1] contiguous required");
+  TORCH_CHECK(n_fft == 256 || n_fft == 512 || n_fft == 1024 || n_fft == 2048 || n_fft == 4096 || n_fft == 8192,
+              "aiko.spectrum_out: n_fft in {256, 512, 1024, 2048, 4096, 8192} required, got ", n_fft);
+  TORCH_CHECK(hop >= 1 && hop <= n_fft, "aiko.spectrum_out: 1 <= hop <= n_fft required, got ", hop);
+  const int64_t B = audio.size(0), n = audio.size(1), K = n_fft / 2 + 1;
+  TORCH_CHECK(n <= INT_MAX, "aiko.spectrum_out: n = ", n, " exceeds 2^31 - 1 samples");
+  const int64_t F = n < n_fft ? 1 : 1 + (n - n_fft) / hop;
+  TORCH_CHECK(F <= 4096, "aiko.spectrum_out: F = ", F, " frames exceed 4096 per call");
+  TORCH_CHECK(B <= 65535, "aiko.spectrum_out: B = ", B, " exceeds the grid limit (65535 streams)");
+  auto is_f32 = [](const at::Tensor& t, std::initializer_list<int64_t> shape) {
+    return t.scalar_type() == at::kFloat && t.is_contiguous() && t.sizes() == at::IntArrayRef(shape);
+  };
+  TORCH_CHECK(is_f32(window, {n_fft}), "aiko.spectrum_out: window fp32 [n_fft = ", n_fft, "] contiguous required");
+  TORCH_CHECK(is_f32(twiddle, {n_fft / 2, 2}), "aiko.spectrum_out: twiddle fp32 [n_fft / 2 = ", n_fft / 2,
+              ", 2] contiguous required");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(twiddle.data_ptr()) % 8 == 0, "aiko.spectrum_out: twiddle 8-byte aligned "
+              "required");
+  TORCH_CHECK(band_start.scalar_type() == at::kInt && band_start.dim() == 1 && band_start.is_contiguous() &&
+                  band_start.size(0) >= 2 && band_start.size(0) <= 65,
+              "aiko.spectrum_out: band_start int32 [bands + 1], 1 <= bands <= 64, contiguous required");
+  const int64_t bands = band_start.size(0) - 1;
+  TORCH_CHECK(std::isfinite(inv_F) && std::isfinite(lo) && std::isfinite(hi) && (double)(float)inv_F == inv_F &&
+                  (double)(float)lo == lo && (double)(float)hi == hi,
+              "aiko.spectrum_out: inv_F, lo and hi finite fp32 values required");
+  TORCH_CHECK(k_lo >= 0 && k_lo <= INT_MAX && k_hi >= -1 && k_hi <= INT_MAX,
+              "aiko.spectrum_out: k_lo >= 0 and k_hi >= -1 required, got ", k_lo, ", ", k_hi);
+  TORCH_CHECK(is_f32(power, {B, F, K}), "aiko.spectrum_out: power fp32 [B, F, K] = [", B, ", ", F, ", ", K,
+              "] contiguous required");
+  TORCH_CHECK(is_f32(amplitudes, {B, K}), "aiko.spectrum_out: amplitudes fp32 [B, K] = [", B, ", ", K,
+              "] contiguous required");
+  TORCH_CHECK(is_f32(band_amplitudes, {B, bands}), "aiko.spectrum_out: band_amplitudes fp32 [B, bands] = [", B, ", ",
+              bands, "] contiguous required");
+  TORCH_CHECK(peak_bins.scalar_type() == at::kInt && peak_bins.dim() == 2 && peak_bins.size(0) == B &&
+                  peak_bins.is_contiguous(),
+              "aiko.spectrum_out: peak_bins int32 [B, max_peaks] contiguous required");
+  const int64_t max_peaks = peak_bins.size(1);
+  TORCH_CHECK(max_peaks >= 1 && max_peaks <= 128, "aiko.spectrum_out: 1 <= max_peaks <= 128 required, got ",
+              max_peaks);
+  TORCH_CHECK(is_f32(peak_amplitudes, {B, max_peaks}), "aiko.spectrum_out: peak_amplitudes fp32 [B, max_peaks] = [", B,
+              ", ", max_peaks, "] contiguous required");
+  TORCH_CHECK(peak_counts.scalar_type() == at::kInt && peak_counts.dim() == 1 && peak_counts.size(0) == B &&
+                  peak_counts.is_contiguous(),
+              "aiko.spectrum_out: peak_counts int32 [B] contiguous required");
+  // no output may overlap an input or another output
+  auto overlap = [](const at::Tensor& x, const at::Tensor& y) {
+    const auto xp = reinterpret_cast<uintptr_t>(x.data_ptr()), yp = reinterpret_cast<uintptr_t>(y.data_ptr());
+    const uintptr_t xn = x.numel() * x.element_size(), yn = y.numel() * y.element_size();
+    return xn > 0 && yn > 0 && xp < yp + yn && yp < xp + xn;
+  };
+  for (int o = 0; o < 6; ++o) {
+    for (int i = 0; i < 4; ++i)
+      TORCH_CHECK(!overlap(*outs[o], *ins[i]), "aiko.spectrum_out: ", out_names[o], " and ", in_names[i], " overlap");
+    for (int p = 0; p < o; ++p)
+      TORCH_CHECK(!overlap(*outs[o], *outs[p]), "aiko.spectrum_out: ", out_names[o], " and ", out_names[p],
+                  " overlap");
+  }
+  check_launch(aiko_spectrum(audio.data_ptr<float>(), window.data_ptr<float>(), twiddle.data_ptr<float>(),
+                             band_start.data_ptr<int>(), power.data_ptr<float>(), amplitudes.data_ptr<float>(),
+                             band_amplitudes.data_ptr<float>(), peak_bins.data_ptr<int>(),
+                             peak_amplitudes.data_ptr<float>(), peak_counts.data_ptr<int>(), (int)B, (long)n, (int)F,
+                             (int)n_fft, (int)hop, (int)bands, (int)max_peaks, (float)inv_F, (float)lo, (float)hi,
+                             (int)k_lo, (int)k_hi, local ? 1 : 0, cur_stream()),
+               "spectrum");
+}
+
+// The scatter graph of a spectrum's peaks (spectrum_ops.hip; step 8 of the rule in ops/spectrum.py): peak_bins /
+// peak_amplitudes [B, max_peaks], peak_counts [B] and bin_px int32 [K] -> image uint8 [B, H, W, 3].  One launch
+void spectrum_graph_out(const at::Tensor& peak_bins, const at::Tensor& peak_amplitudes, const at::Tensor& peak_counts,
+                        const at::Tensor& bin_px, double y_max, at::IntArrayRef color, at::Tensor& image) {
+  const at::Tensor* ts[5] = {&peak_bins, &peak_amplitudes, &peak_counts, &bin_px, &image};
+  const char* names[5] = {"peak_bins", "peak_amplitudes", "peak_counts", "bin_px", "image"};
+  for (int i = 0; i < 5; ++i) check_cuda(*ts[i], names[i]);
+  for (int i = 1; i < 5; ++i)
+    TORCH_CHECK(ts[i]->device() == peak_bins.device(), "aiko.spectrum_graph_out: tensors on different devices");
+  TORCH_CHECK(peak_bins.scalar_type() == at::kInt && peak_bins.dim() == 2 && peak_bins.is_contiguous() &&
+                  peak_bins.size(0) >= 1,
+              "aiko.spectrum_graph_out: peak_bins int32 [B, max_peaks] contiguous required");
+  const int64_t B = peak_bins.size(0), max_peaks = peak_bins.size(1);
+  TORCH_CHECK(max_peaks >= 1 && max_peaks <= 128, "aiko.spectrum_graph_out: 1 <= max_peaks <= 128 required, got ",
+              max_peaks);
+  TORCH_CHECK(B <= 65535, "aiko.spectrum_graph_out: B = ", B, " exceeds the grid limit (65535 streams)");
+  TORCH_CHECK(peak_amplitudes.scalar_type() == at::kFloat && peak_amplitudes.is_contiguous() &&
+                  peak_amplitudes.sizes() == peak_bins.sizes(),
+              "aiko.spectrum_graph_out: peak_amplitudes fp32 [B, max_peaks] = [", B, ", ", max_peaks,
+              "] contiguous required");
+  TORCH_CHECK(peak_counts.scalar_type() == at::kInt && peak_counts.dim() == 1 && peak_counts.size(0) == B &&
+                  peak_counts.is_contiguous(),
+              "aiko.spectrum_graph_out: peak_counts int32 [B] contiguous required");
+  TORCH_CHECK(bin_px.scalar_type() == at::kInt && bin_px.dim() == 1 && bin_px.size(0) >= 1 &&
+                  bin_px.size(0) <= 4097 && bin_px.is_contiguous(),
+              "aiko.spectrum_graph_out: bin_px int32 [K <= 4097] contiguous required");
+  TORCH_CHECK(image.scalar_type() == at::kByte && image.dim() == 4 && image.size(0) == B && image.size(3) == 3 &&
+                  image.is_contiguous(),
+              "aiko.spectrum_graph_out: image uint8 [B, H, W, 3] contiguous required, B = ", B);
+  const int64_t H = image.size(1), W = image.size(2);
+  TORCH_CHECK(H >= 16 && H <= 4096 && W >= 16 && W <= 4096,
+              "aiko.spectrum_graph_out: 16 <= H, W <= 4096 required, got ", H, " x ", W);
+  TORCH_CHECK(std::isfinite(y_max) && y_max > 0.0, "aiko.spectrum_graph_out: y_max > 0 required, got ", y_max);
+  TORCH_CHECK(color.size() == 3, "aiko.spectrum_graph_out: color [r, g, b] required");
+  for (int64_t c : color) TORCH_CHECK(c >= 0 && c <= 255, "aiko.spectrum_graph_out: color in 0..255 required, got ", c);
+  auto overlap = [](const at::Tensor& x, const at::Tensor& y) {
+    const auto xp = reinterpret_cast<uintptr_t>(x.data_ptr()), yp = reinterpret_cast<uintptr_t>(y.data_ptr());
+    const uintptr_t xn = x.numel() * x.element_size(), yn = y.numel() * y.element_size();
+    return xn > 0 && yn > 0 && xp < yp + yn && yp < xp + xn;
+  };
+  for (int i = 0; i < 4; ++i)
+    TORCH_CHECK(!overlap(image, *ts[i]), "aiko.spectrum_graph_out: image and ", names[i], " overlap");
+  check_launch(aiko_spectrum_graph(peak_bins.data_ptr<int>(), peak_amplitudes.data_ptr<float>(),
+                                   peak_counts.data_ptr<int>(), bin_px.data_ptr<int>(), image.data_ptr(), (int)B, (int)H,
+                                   (int)W, (int)bin_px.size(0), (int)max_peaks, y_max, (int)color[0], (int)color[1],
+                                   (int)color[2], cur_stream()),
+               "spectrum_graph");
+}
+
 // Baseline JPEG (jpeg_ops.hip; the rule is in ops/jpeg.py): raw planar frames [B, frame_bytes] (fmt 1: i420,
 // 2: i444) -> one JFIF stream per frame in stream [B, cap], its length (-1: overflow) in nbytes [B].  tables is
 // ops.jpeg.device_tables' tensor (864 words, then header_len bytes of header); workspace holds an int32 and
@@ -2255,6 +2397,8 @@ TORCH_LIBRARY(aiko, m) {
   m.def("marker_detect_out(Tensor frames, int modules, int cell, int contrast, int min_side, int max_cand, int passes, Tensor(a!) det, Tensor(b!) count, Tensor(c!) corners, Tensor(d!) ids, Tensor(e!) cands, Tensor(f!) mask, Tensor(g!) work) -> ()");
   m.def("motion_detect_out(Tensor frames, Tensor bg, Tensor seen, int cell, int threshold, int learn_shift, bool learn_moving, int warmup, int min_cells, Tensor(a!) bg_out, Tensor(b!) seen_out, Tensor(c!) det, Tensor(d!) count, Tensor(e!) mask, Tensor(f!) cells) -> ()");
   m.def("voice_activity_out(Tensor audio, Tensor state, int frame, int threshold, int min_level, int up_shift, int speech_shift, int down_shift, int warmup, int attack, int hang, int max_zc, int window, Tensor(a!) state_out, Tensor(b!) level, Tensor(c!) zc, Tensor(d!) mask, Tensor(e!) seg, Tensor(f!) count, Tensor(g!) speech, Tensor(h!) silent) -> ()");
+  m.def("spectrum_out(Tensor audio, Tensor window, Tensor twiddle, Tensor band_start, int n_fft, int hop, float inv_F, float lo, float hi, int k_lo, int k_hi, bool local, Tensor(a!) power, Tensor(b!) amplitudes, Tensor(c!) band_amplitudes, Tensor(d!) peak_bins, Tensor(e!) peak_amplitudes, Tensor(f!) peak_counts) -> ()");
+  m.def("spectrum_graph_out(Tensor peak_bins, Tensor peak_amplitudes, Tensor peak_counts, Tensor bin_px, float y_max, int[] color, Tensor(a!) image) -> ()");
   m.def("jpeg_encode_out(Tensor raw, int height, int width, int fmt, Tensor tables, int header_len, int seg_cap, Tensor(a!) stream, Tensor(b!) nbytes, Tensor(c!) workspace) -> ()");
   m.def("jpeg_decode_out(Tensor data, Tensor nbytes, Tensor desc, int height, int width, int fmt, int max_intervals, Tensor(a!) raw, Tensor(b!) status, Tensor(c!) workspace) -> ()");
   m.def("resample_out(Tensor pcm, Tensor hist, Tensor filt, int L, int M, Tensor(a!) out, Tensor(b!) hist_out) -> ()");
@@ -2307,6 +2451,8 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("marker_detect_out", &marker_detect_out);
   m.impl("motion_detect_out", &motion_detect_out);
   m.impl("voice_activity_out", &voice_activity_out);
+  m.impl("spectrum_out", &spectrum_out);
+  m.impl("spectrum_graph_out", &spectrum_graph_out);
   m.impl("jpeg_encode_out", &jpeg_encode_out);
   m.impl("jpeg_decode_out", &jpeg_decode_out);
   m.impl("zero_border_rows_", &zero_border_rows_);

@@ -4,3 +4,4 @@ from .audio_ingest import AudioResample  # noqa: F401
 from .egress import FrameDownload, RgbToYuv  # noqa: F401
 from .ingest import YuvToRgb  # noqa: F401
 from .marker import MarkerDetector, MarkerResults  # noqa: F401
+from .spectrum import AudioSpectrum, SpectrumResults  # noqa: F401

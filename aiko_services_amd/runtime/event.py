@@ -243,7 +243,7 @@ class EventEngine:
                 h(item, item_type)
 
     def _priority_pending(self):
-        for mb in self._mailboxes.values():
+        for mb in list(self._mailboxes.values()):      # a snapshot: other threads add and remove mailboxes
             if mb.priority and mb.queue:
                 return True
         return False
@@ -276,7 +276,7 @@ class EventEngine:
     def _has_work(self):
         if self._queue:
             return True
-        for mb in self._mailboxes.values():
+        for mb in list(self._mailboxes.values()):
             if mb.queue:
                 return True
         return False
