@@ -2252,7 +2252,9 @@ void embed_tokens_out(const at::Tensor& ids, const at::Tensor& pos, const at::Te
 
 // One query row per sequence against K/V rows [B*S, >= H*64] (sequence b's key j at row b*S+j).
 // With ``pos`` (device int32 [1]) the step appends ``knew``/``vnew`` [B, >= H*64] at row pos of
-// every sequence and attends keys 0..pos; otherwise it attends keys 0..T-1.
+// every sequence and attends keys 0..pos; otherwise it attends keys 0..T-1.  The kernel reads
+// pos on the device: a value < 0 is treated as 0, a value >= S appends nothing and attends the
+// S cached keys, so no access leaves the cache.
 void attn_decode_out(const at::Tensor& q, at::Tensor& k, at::Tensor& v, at::Tensor& o, int64_t B, int64_t H,
                      int64_t S, int64_t T, const c10::optional<at::Tensor>& pos,
                      const c10::optional<at::Tensor>& knew, const c10::optional<at::Tensor>& vnew, double scale,

@@ -71,7 +71,10 @@ __device__ __forceinline__ float dot8(const uint4 k, const float* q) {
   return s;
 }
 
-// k/v: row j of sequence b at (b*S + j)*ld + h*64.  len = pos ? *pos + 1 : T.
+// k/v: row j of sequence b at (b*S + j)*ld + h*64.  len = pos ? *pos + 1 : T.  Append mode keeps
+// every access inside the S cache rows whatever *pos holds: *pos < 0 is treated as 0, and with
+// *pos >= S nothing is appended and keys 0..S-1 are attended.  A NaN key makes its head's 64
+// outputs NaN (the sum l is NaN; only an exactly zero sum gives a zero row).
 // Workgroup (split, b*H+h) covers key chunks split, split + nsplit, ... of KC keys with an online
 // softmax.  Thread t owns 16-byte column chunk c = t & 7 (head dims 8c .. 8c+7) of keys kg,
 // kg + 32, ... of a chunk (kg = t >> 3): a score is an 8-lane shuffle reduction and every K/V
@@ -91,13 +94,19 @@ __global__ __launch_bounds__(kDecKC) void attn_decode_kernel(
   const int b = bh / H, h = bh - b * H;
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   const int c = tid & 7, kg = tid >> 3;
-  const int papp = pos ? *pos : -1;            // appended position (append mode)
-  const int len = pos ? papp + 1 : T;
+  // appended position (append mode): *pos < 0 counts as 0; *pos >= S (a full cache) appends
+  // nothing (papp = -1) and attends the S cached keys, so no store or load leaves the cache
+  int papp = -1, len = T;
+  if (pos) {
+    const int p = *pos;
+    papp = p < 0 ? 0 : (p >= S ? -1 : p);
+    len = p >= S ? S : papp + 1;
+  }
   const long kb = (long)b * S;
   const bf16_t* knr = knew ? knew + (long)b * ldnew + h * kDecDh : nullptr;
   const bf16_t* vnr = vnew ? vnew + (long)b * ldnew + h * kDecDh : nullptr;
   // the split owning the appended row writes it into the cache (read by later steps only)
-  if (knr && tid < 16 && (papp / kDecKC) % nsplit == split) {
+  if (knr && papp >= 0 && tid < 16 && (papp / kDecKC) % nsplit == split) {
     const int cc = (tid & 7) * 8;
     if (tid < 8)
       *reinterpret_cast<uint4*>(k + (kb + papp) * ldk + h * kDecDh + cc) = *reinterpret_cast<const uint4*>(knr + cc);
@@ -182,7 +191,7 @@ __global__ __launch_bounds__(kDecKC) void attn_decode_kernel(
 #pragma unroll 8
   for (int g = 0; g < KG; ++g) r += accs[g][tid];
   if (nsplit == 1) {
-    o[(long)b * ldo + h * kDecDh + tid] = f2bf(l > 0.f ? r / l : 0.f);
+    o[(long)b * ldo + h * kDecDh + tid] = f2bf(l == 0.f ? 0.f : r / l);   // a NaN sum (NaN key) propagates
     return;
   }
   opart[((long)bh * nsplit + split) * kDecDh + tid] = r;
@@ -206,7 +215,7 @@ __global__ void attn_decode_combine(const float* __restrict__ opart, const float
     L += w * ml[2 * s + 1];
     acc += w * opart[((long)bh * nsplit + s) * kDecDh + d];
   }
-  o[(long)b * ldo + h * kDecDh + d] = f2bf(L > 0.f ? acc / L : 0.f);
+  o[(long)b * ldo + h * kDecDh + d] = f2bf(L == 0.f ? 0.f : acc / L);
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -64,7 +64,9 @@ def attn_decode(q, k, v, out, B: int, H: int, S: int, T: int, scale: float, work
                 pos=None, knew=None, vnew=None):
     """Flash-decoding attention of one query row per sequence (head dim 64); see
     ``csrc/kernels/decode_ops.hip``.  With ``pos`` the new key/value rows are appended at
-    row ``pos`` of every sequence's cache first and keys 0..pos are attended."""
+    row ``pos`` of every sequence's cache first and keys 0..pos are attended.  ``pos`` is read on
+    the device: a value below 0 is treated as 0; with ``pos >= S`` (a full cache) nothing is
+    appended and the S cached keys are attended, so no access leaves the cache."""
     torch.ops.aiko.attn_decode_out(q, k, v, out, B, H, S, T, pos, knew, vnew, float(scale), work)
     return out
 
