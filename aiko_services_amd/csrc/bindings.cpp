@@ -1232,6 +1232,10 @@ void topk_nms_out(const at::Tensor& boxes, const at::Tensor& scores, const at::T
   check_cuda(det, "det");
   check_cuda(count, "count");
   TORCH_CHECK(params.size() == 8, "aiko.topk_nms_out: params = [conf, iou, max_wh, gain, pad_l, pad_t, img_w, img_h]");
+  // the selection keys are the scores' fp32 bits, ordered like the scores only from +0 up: with
+  // conf < 0 a score of 0.0 would get key 0 ("no candidate") and negative scores the largest keys
+  TORCH_CHECK(params[0] >= 0.0 && params[1] == params[1],
+              "aiko.topk_nms_out: conf must be >= 0 and neither conf nor iou NaN");
   TORCH_CHECK(scores.scalar_type() == at::kFloat && scores.dim() == 2 && scores.is_contiguous(),
               "aiko.topk_nms_out: scores fp32 [B, A]");
   const int64_t B = scores.size(0), A = scores.size(1);
