@@ -1,9 +1,9 @@
 """In-tree native build for aiko_services_amd (gfx950 only).
 
 Compiles every ``csrc/kernels/*.hip`` (device code, no torch headers: seconds per file),
-``csrc/runtime/*.cpp`` and ``csrc/bindings.cpp`` (torch operator registrations) with
-``hipcc --offload-arch=gfx950`` and links them into ``aiko_services_amd/_C.so``, which is
-loaded with ``torch.ops.load_library``.  Objects are cached under ``csrc/.build`` keyed by a
+``csrc/runtime/*.cpp`` and ``csrc/bindings/*.cpp`` (torch operator registrations, one file per
+domain) with ``hipcc --offload-arch=gfx950`` and links them into ``aiko_services_amd/_C.so``,
+which is loaded with ``torch.ops.load_library``.  Objects are cached under ``csrc/.build`` keyed by a
 hash of the source + flags + headers, so rebuilds only touch changed files.
 
 No hipify, no CUDA, no multi-arch: the code objects are built for MI355X (gfx950) alone.
@@ -54,7 +54,7 @@ def _hash(paths, flags) -> str:
 def sources():
     kernels = sorted((CSRC / "kernels").glob("*.hip"))
     runtime = sorted((CSRC / "runtime").glob("*.cpp"))
-    return kernels, runtime, CSRC / "bindings.cpp"
+    return kernels, runtime, sorted((CSRC / "bindings").glob("*.cpp"))
 
 
 def _compile(src: Path, flags, headers) -> Path:
@@ -108,7 +108,11 @@ def build(force: bool = False, debug: bool = False, jobs: int | None = None, ver
     except RuntimeError as e:
         print(f"[aiko build] host modules skipped (pure-Python fallbacks in use): {e}", file=sys.stderr)
     BUILD.mkdir(exist_ok=True)
-    kernels, runtime, binding = sources()
+    kernels, runtime, bindings = sources()
+    stems = [s.stem for s in (*kernels, *runtime, *bindings)]
+    clash = sorted({s for s in stems if stems.count(s) > 1})
+    if clash:           # objects are named by stem: one would overwrite the other
+        raise RuntimeError(f"sources share a stem: {', '.join(clash)}")
     tinc, tlib = _torch_paths()
     opt = ["-O0", "-g"] if debug else ["-O3"]
     common = ["-fPIC", "-std=c++17", *opt, "-Wno-unused-result", "-Wno-unused-command-line-argument"]
@@ -123,7 +127,7 @@ def build(force: bool = False, debug: bool = False, jobs: int | None = None, ver
     host_flags = [f for f in host_flags if not f.startswith("-D_GLIBCXX_USE_CXX11_ABI")]
     host_flags.append(f"-D_GLIBCXX_USE_CXX11_ABI={abi}")
     headers_dev = sorted((CSRC / "kernels").glob("*.h"))
-    headers_host = sorted((CSRC / "runtime").glob("*.h")) + headers_dev
+    headers_host = sorted((CSRC / "runtime").glob("*.h")) + sorted((CSRC / "bindings").glob("*.h")) + headers_dev
     if force:
         for o in BUILD.glob("*.o"):
             o.unlink()
@@ -131,7 +135,7 @@ def build(force: bool = False, debug: bool = False, jobs: int | None = None, ver
     work = [(k, dev_flags, headers_dev) for k in kernels]
     # runtime .cpp and bindings are host code that uses the HIP runtime API only
     work += [(r, [*host_flags, f"--offload-arch={ARCH}"], headers_host) for r in runtime]
-    work.append((binding, [*host_flags, f"--offload-arch={ARCH}"], headers_host))
+    work += [(b, [*host_flags, f"--offload-arch={ARCH}"], headers_host) for b in bindings]
     with cf.ThreadPoolExecutor(jobs) as ex:
         objs = list(ex.map(lambda a: _compile(*a), work))
     link_key = _hash(objs, ["link"])

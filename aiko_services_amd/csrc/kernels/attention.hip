@@ -26,6 +26,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -14,6 +14,7 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -71,6 +71,7 @@
 #include <type_traits>
 
 #include "conv_common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

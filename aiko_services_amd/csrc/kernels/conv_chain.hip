@@ -25,6 +25,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 
@@ -254,10 +255,6 @@ __global__ __launch_bounds__(512, (N1 <= 256 ? 2 : 1)) void conv_chain_kernel(
 }
 
 }  // namespace aiko
-
-extern "C" int aiko_conv_chain2(const void* A, const void* W1, const float* b1, const void* R, void* Y,
-                                const void* W2, const float* b2, void* Z, int M, int K1, int N1, int N2,
-                                int grid, hipStream_t stream);
 
 extern "C" int aiko_conv_chain(const void* A, const void* W1, const float* b1, const void* R, void* Y,
                                const void* W2, const float* b2, void* Z, const void* A2, int M, int K1, int N1, int N2,

@@ -33,6 +33,7 @@
 
 #include "conv_common.h"
 #include "conv_wide_stage.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -16,6 +16,7 @@
 // expect.  Conv zero padding (and rows / channels past the edge) are fetched from a zeroed
 // 16-B global page instead of being predicated away.
 #include "conv_common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -20,6 +20,7 @@
 // residual add, ReLU/SiLU and the bf16 store all run on 16-byte contiguous row pieces.
 // Workgroup ids are remapped XCD-aware so that the N tiles of one M panel share an L2.
 #include "conv_common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -17,6 +17,7 @@
 //     after the activation), activation and an 8-byte store straight from the accumulators — no
 //     LDS round trip.  Output and residual may be channel slices (pixel pitches ldy / ldr).
 #include "conv_common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -26,6 +26,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -32,6 +32,7 @@
 #include <utility>
 
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

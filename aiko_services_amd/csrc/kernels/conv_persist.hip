@@ -29,6 +29,7 @@
 // + fragment reads of both operands, ~144 KB per CU-step at 2 WG/CU) exceeds the matrix pipe's
 // time, so the LDS, not the memory latency, is the co-limit.  Kept as a tuner candidate.
 #include "conv_common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -32,6 +32,7 @@
 // three 32 KB blocks in flight per CU across tile boundaries the kernel still spends ~5 us per
 // 128 x 128 tile (17 % MFMA, ~37 % LDS, 3.8 TB/s HBM).  Kept as a tuner candidate.
 #include "conv_common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

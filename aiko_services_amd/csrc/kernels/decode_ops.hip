@@ -23,6 +23,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -13,6 +13,7 @@
 #include <cstring>
 
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

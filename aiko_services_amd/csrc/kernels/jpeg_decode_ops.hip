@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "jpeg_decode_core.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -20,6 +20,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "aiko_api.h"
+
 namespace aiko {
 
 constexpr int JP_THREADS = 256;

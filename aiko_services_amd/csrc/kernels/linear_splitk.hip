@@ -11,6 +11,7 @@
 // and the activations as B (columns = rows m of x): lane (fr, fq) ends with output channels
 // 4 fq .. 4 fq + 3 of row fr — one 16-B fp32 store per accumulator tile.
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

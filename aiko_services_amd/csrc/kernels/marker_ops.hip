@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aiko_api.h"
+
 namespace aiko {
 
 constexpr int MK_TW = 128, MK_TH = 32;               // pixels per tile: one workgroup (MO_TW, MO_TH)

@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aiko_api.h"
+
 namespace aiko {
 
 constexpr int MO_TW = 128, MO_TH = 32;               // pixels per tile: one workgroup (RD_TW, RD_TH)

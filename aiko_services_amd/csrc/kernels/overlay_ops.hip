@@ -10,6 +10,7 @@
 #include <stdint.h>
 
 #include "roi_rect.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

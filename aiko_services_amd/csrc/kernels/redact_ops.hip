@@ -17,6 +17,7 @@
 #include <stdint.h>
 
 #include "roi_rect.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

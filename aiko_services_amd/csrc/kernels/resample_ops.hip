@@ -26,6 +26,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aiko_api.h"
+
 namespace aiko {
 
 constexpr int RS_THREADS = 256;

@@ -23,6 +23,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aiko_api.h"
+
 namespace aiko {
 
 constexpr int SP_THREADS = 256;

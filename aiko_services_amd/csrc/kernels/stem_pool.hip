@@ -25,6 +25,7 @@
 //
 // Rounding is identical to the unfused path: the stem value is rounded to bf16 before the max.
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

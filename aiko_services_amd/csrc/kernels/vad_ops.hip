@@ -17,6 +17,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aiko_api.h"
+
 namespace aiko {
 
 constexpr int VA_WAVES = 4;                           // frames per workgroup of the frame pass

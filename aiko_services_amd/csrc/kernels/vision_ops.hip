@@ -3,6 +3,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "aiko_api.h"
 
 namespace aiko {
 

@@ -15,6 +15,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aiko_api.h"
+
 namespace aiko {
 
 constexpr int YUV_THREADS = 256;

@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "aiko_api.h"
+
 // 0: each lane loads its own 48 RGB bytes per row (three uint4; across a wave 64 pieces 48 B apart,
 // every line of the 3 KiB read in full by the three loads together).  1: a wave's row comes through
 // LDS so that each load of a wave is 1 KiB contiguous, the mirror of yuv_ops.hip's store side.

@@ -625,6 +625,10 @@ def test_nms_refusals(native):
         DT.topk_nms(boxes.half(), scores, cls, **ok)
     with pytest.raises(RuntimeError, match="cls int32"):
         DT.topk_nms(boxes, scores, cls.long(), **ok)
+    with pytest.raises(RuntimeError, match="det fp32"):                       # the operator's own check
+        torch.ops.aiko.topk_nms_out(boxes, scores, cls, 64, [0.25, 0.5, 7680.0, 1.0, 0.0, 0.0, 640.0, 640.0],
+                                    torch.empty(2, 16, 6, dtype=torch.float64, device=DEV),
+                                    torch.empty(2, dtype=torch.int32, device=DEV))
     for bad in ({"conf": -0.25}, {"conf": float("nan")}, {"iou": float("nan")}, {"conf": NEG_INF}):
         with pytest.raises(RuntimeError, match="conf must be >= 0"):
             DT.topk_nms(boxes, scores, cls, **{**ok, **bad})

@@ -182,6 +182,13 @@ def test_refusals(native):
                                          torch.empty(B, dtype=torch.int32, device="cuda"),
                                          torch.empty(B, gh, gw, dtype=torch.uint8, device="cuda"),
                                          torch.empty(B, dtype=torch.int32, device="cuda"))
+    with pytest.raises(RuntimeError, match="grid limit"):                  # 65536 frames: past the launch grid
+        torch.ops.aiko.motion_detect_out(torch.zeros(65536, 1, 1, 3, dtype=torch.uint8, device="cuda"), state.bg,
+                                         state.seen, 16, 12, 4, True, 1, 2, state.bg.clone(), state.seen.clone(),
+                                         torch.empty(B, 16, 6, device="cuda"),
+                                         torch.empty(B, dtype=torch.int32, device="cuda"),
+                                         torch.empty(B, gh, gw, dtype=torch.uint8, device="cuda"),
+                                         torch.empty(B, dtype=torch.int32, device="cuda"))
     # the grid limits: 1080p at cell 8 is 135 x 240 = 32400 cells; 257 columns; 257 rows
     for h, w in ((1080, 1920), (8, 2056), (2056, 8)):
         big = torch.zeros(1, h, w, 3, dtype=torch.uint8, device="cuda")

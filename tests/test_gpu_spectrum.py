@@ -183,6 +183,10 @@ def test_refusals(native):
     with pytest.raises(RuntimeError, match="16 <= H, W <= 4096"):
         torch.ops.aiko.spectrum_graph_out(i32(1, 4), torch.zeros(1, 4, device="cuda"), i32(1), i32(129), 12.0,
                                           [0, 255, 0], torch.empty(1, 8, 64, 3, dtype=torch.uint8, device="cuda"))
+    both = torch.zeros(16 * 16 * 3, dtype=torch.uint8, device="cuda")       # the image over its own peaks
+    with pytest.raises(RuntimeError, match="image and peak_amplitudes overlap"):
+        torch.ops.aiko.spectrum_graph_out(i32(1, 4), both[:16].view(torch.float32).view(1, 4), i32(1), i32(129), 12.0,
+                                          [0, 255, 0], both.view(1, 16, 16, 3))
     with pytest.raises(RuntimeError, match="max_peaks"):
         spectrum_graph(i32(1, 129), torch.zeros(1, 129, device="cuda"), i32(1), n_fft=256, height=16, width=16)
     # the extremes inside the limits: 4096 frames of one stream
