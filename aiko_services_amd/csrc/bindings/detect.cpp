@@ -1,5 +1,5 @@
 // torch.ops.aiko.*: the detect head's tail and what works on its detections (decode, NMS, crop,
-// draw, redact, track), and motion and marker detection, which write detector rows.
+// warp, draw, redact, track), and motion and marker detection, which write detector rows.
 // Each operator validates shapes / dtypes / devices on the host (checks.h holds the shared
 // checks) and launches on the caller's current HIP stream.
 #include "checks.h"
@@ -100,6 +100,53 @@ void roi_crop_out(const at::Tensor& frames, const at::Tensor& det, const at::Ten
   check_launch(aiko_roi_crop_u8(frames.data_ptr(), det.data_ptr<float>(), count.data_ptr<int>(), crops.data_ptr(),
                                 rois.data_ptr<int>(), B, H, W, max_det, k, Ho, Wo, (float)margin, cur_stream()),
                "roi_crop_u8");
+}
+
+// patches[b*k + i] <- the quad quads[b, i] (i < min(count[b], k), coordinates in -4096..8191, not
+// degenerate) of frame b rectified to patches' [Ho, Wo] (warp_ops.hip; the rule is in ops/warp.py);
+// valid[b*k + i] <- 1 for such a slot; other slots zero in both.  margin: sixteenths of the side added
+// all round; origin 1: the coordinates are pixel centres, 0: pixel edges
+void quad_warp_out(const at::Tensor& frames, const at::Tensor& quads, const at::Tensor& count, int64_t k,
+                   int64_t margin, int64_t origin, at::Tensor& patches, at::Tensor& valid) {
+  const at::Tensor* ins[3] = {&frames, &quads, &count};
+  const char* in_names[3] = {"frames", "quads", "count"};
+  const at::Tensor* outs[2] = {&patches, &valid};
+  const char* out_names[2] = {"patches", "valid"};
+  check_cuda_all(ins, in_names);
+  check_cuda_all(outs, out_names);
+  check_same_device(ins, outs, "quad_warp_out");
+  check_frames_u8(frames, "quad_warp_out");
+  TORCH_CHECK(frames.numel() >= 4, "aiko.quad_warp_out: frames uint8 [B, H, W, 3] contiguous required");
+  const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2);
+  TORCH_CHECK(H <= 4096 && W <= 4096, "aiko.quad_warp_out: H = ", H, ", W = ", W,
+              " exceed the frame limit (4096 pixels a side)");
+  TORCH_CHECK(quads.scalar_type() == at::kInt && quads.dim() == 4 && quads.size(0) == B && quads.size(1) >= 1 &&
+                  quads.size(2) == 4 && quads.size(3) == 2 && quads.is_contiguous(),
+              "aiko.quad_warp_out: quads int32 [B, Kq, 4, 2] contiguous required");
+  const int64_t Kq = quads.size(1);
+  TORCH_CHECK(count.scalar_type() == at::kInt && count.dim() == 1 && count.size(0) == B && count.is_contiguous(),
+              "aiko.quad_warp_out: count int32 [B] contiguous required");
+  TORCH_CHECK(k >= 1 && k <= Kq, "aiko.quad_warp_out: 1 <= k <= Kq (", Kq, ") required, got ", k);
+  TORCH_CHECK(margin >= 0 && margin <= 64, "aiko.quad_warp_out: margin in 0..64 (sixteenths of the side) required, "
+              "got ", margin);
+  TORCH_CHECK(origin == 0 || origin == 1, "aiko.quad_warp_out: origin 1 (pixel centres) or 0 (pixel edges) required, "
+              "got ", origin);
+  TORCH_CHECK(B * k <= 65535, "aiko.quad_warp_out: B * k = ", B * k, " slots exceed the grid limit (65535)");
+  TORCH_CHECK(patches.scalar_type() == at::kByte && patches.dim() == 4 && patches.size(0) == B * k &&
+                  patches.size(3) == 3 && patches.is_contiguous(),
+              "aiko.quad_warp_out: patches uint8 [B*k, Ho, Wo, 3] contiguous required");
+  const int64_t Ho = patches.size(1), Wo = patches.size(2);
+  TORCH_CHECK(Ho >= 1 && Wo >= 4 && Wo % 4 == 0, "aiko.quad_warp_out: patch width must be a multiple of 4, got ", Wo);
+  TORCH_CHECK(Ho <= 4096 && Wo <= 4096, "aiko.quad_warp_out: patch side <= 4096 required, got ", Ho, " x ", Wo);
+  TORCH_CHECK(valid.scalar_type() == at::kInt && valid.dim() == 1 && valid.size(0) == B * k && valid.is_contiguous(),
+              "aiko.quad_warp_out: valid int32 [B*k] contiguous required");
+  TORCH_CHECK(aligned(patches, 4) && aligned(valid, 4), "aiko.quad_warp_out: patches and valid 4-byte aligned");
+  // no output may overlap an input or the other output
+  check_no_overlap(outs, out_names, ins, in_names, "quad_warp_out");
+  check_launch(aiko_quad_warp_u8(frames.data_ptr(), quads.data_ptr<int>(), count.data_ptr<int>(), patches.data_ptr(),
+                                 valid.data_ptr<int>(), (int)B, (int)H, (int)W, (int)Kq, (int)k, (int)Ho, (int)Wo,
+                                 (int)margin, (int)origin, cur_stream()),
+               "quad_warp_u8");
 }
 
 // out <- frames with the boxes and labels of det[b, i] (i < min(count[b], k), coordinates finite)
@@ -391,6 +438,7 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("yolo_decode_out", &yolo_decode_out);
   m.impl("topk_nms_out", &topk_nms_out);
   m.impl("roi_crop_out", &roi_crop_out);
+  m.impl("quad_warp_out", &quad_warp_out);
   m.impl("draw_detections_out", &draw_detections_out);
   m.impl("redact_detections_out", &redact_detections_out);
   m.impl("track_detections_out", &track_detections_out);

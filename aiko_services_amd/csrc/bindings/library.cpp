@@ -8,6 +8,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("upsample2x_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("resize_u8_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("roi_crop_out(Tensor frames, Tensor det, Tensor count, int k, float margin, Tensor(a!) crops, Tensor(b!) rois) -> ()");
+  m.def("quad_warp_out(Tensor frames, Tensor quads, Tensor count, int k, int margin, int origin, Tensor(a!) patches, Tensor(b!) valid) -> ()");
   m.def("draw_detections_out(Tensor frames, Tensor det, Tensor count, int k, Tensor? labels, Tensor? scores, Tensor names, Tensor font, Tensor palette, int glyph_width, int thickness, int text_scale, float margin, bool show_score, Tensor(a!) out) -> ()");
   m.def("redact_detections_out(Tensor frames, Tensor det, Tensor count, int k, Tensor? labels, Tensor? select, int mode, int block, int fill_rgb, float margin, Tensor(a!) out) -> ()");
   m.def("yuv_to_rgb_out(Tensor raw, int height, int width, int format, float[] coeffs, int round_mode, Tensor(a!) out) -> ()");

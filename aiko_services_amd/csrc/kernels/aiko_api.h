@@ -133,6 +133,10 @@ int aiko_marker_detect(const void* frames, float* det, int* count, int* corners,
                        void* work, int B, int H, int W, int N, int cell, int contrast, int min_side, int max_cand,
                        int max_det, int passes, hipStream_t stream);
 
+// ---- warp_ops.hip: projective warp selected by quads
+int aiko_quad_warp_u8(const void* frames, const int* quads, const int* count, void* patches, int* valid, int B, int H,
+                      int W, int Kq, int K, int Ho, int Wo, int margin, int origin, hipStream_t stream);
+
 // ---- yuv_ops.hip / yuv_out_ops.hip: raw YUV frames in and out
 int aiko_yuv_to_rgb_u8(const void* raw, void* out, int B, int H, int W, int fmt, const float* coef, int half,
                        hipStream_t stream);

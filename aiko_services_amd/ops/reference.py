@@ -1263,3 +1263,79 @@ def spectrum_graph_ref(peak_bins, peak_amplitudes, peak_counts, *, n_fft: int = 
                 for dx in (-1, 0, 1):
                     img[b, min(max(py + dy, 0), H - 1), min(max(px + dx, 0), W - 1)] = color
     return torch.from_numpy(img)
+
+
+# ---- projective warp --------------------------------------------------------------------------
+
+def warp_coefficients_ref(quad, origin: str = "centre"):
+    """Step 2 of ``ops/warp.py`` in Python ints (exact): ``(G, Hh, den, A, Bx, Cx, D, E, Cy)`` of the
+    quad ``[(x, y)] * 4`` with ``den > 0``, or None if ``den == 0``."""
+    from .warp import ORIGINS
+    o = ORIGINS[origin]
+    (X0, Y0), (X1, Y1), (X2, Y2), (X3, Y3) = [(2 * int(x) + o, 2 * int(y) + o) for x, y in quad]
+    dx1, dx2, sx = X1 - X2, X3 - X2, X0 - X1 + X2 - X3
+    dy1, dy2, sy = Y1 - Y2, Y3 - Y2, Y0 - Y1 + Y2 - Y3
+    den = dx1 * dy2 - dy1 * dx2
+    if den == 0:
+        return None
+    G, Hh = sx * dy2 - sy * dx2, dx1 * sy - dy1 * sx
+    A, Bx, Cx = den * (X1 - X0) + G * X1, den * (X3 - X0) + Hh * X3, den * X0
+    D, E, Cy = den * (Y1 - Y0) + G * Y1, den * (Y3 - Y0) + Hh * Y3, den * Y0
+    c = (G, Hh, den, A, Bx, Cx, D, E, Cy)
+    return tuple(-x for x in c) if den < 0 else c
+
+
+def warp_quads_ref(frames: torch.Tensor, quads: torch.Tensor, count: torch.Tensor, k: int, size=(224, 224),
+                   margin: int = 0, origin: str = "centre"):
+    """The definition of :func:`aiko_services_amd.ops.warp.warp_quads` on the CPU: ``(patches,
+    valid)``, uint8 ``[B*k, Ho, Wo, 3]`` and int32 ``[B*k]``.  The coefficients are Python ints, the
+    per-pixel arithmetic numpy float64 vectorised over the patch (one rounding per operation, numpy
+    contracts nothing), the sampling numpy int64.  Any ``Wo`` is taken: the multiple of 4 is the
+    kernel's store width, not the rule's."""
+    import numpy as np
+
+    from .warp import COORD_MAX, COORD_MIN, MAX_SIDE, check_parameters
+    Ho, Wo = int(size[0]), int(size[1])
+    check_parameters(k, (Ho, 4), margin, origin)
+    if not 1 <= Wo <= MAX_SIDE:
+        raise ValueError(f"warp_quads_ref: 1 <= Wo <= {MAX_SIDE} required, got {Wo}")
+    f = frames.detach().cpu().numpy().astype(np.int64)
+    q = quads.detach().cpu().numpy().astype(np.int64)
+    n = count.detach().cpu().numpy().astype(np.int64)
+    B, H, W, _ = f.shape
+    k, m = int(k), int(margin)
+    if H > MAX_SIDE or W > MAX_SIDE:
+        raise ValueError(f"warp_quads_ref: H, W <= {MAX_SIDE} required, got {H} x {W}")
+    if q.ndim != 4 or q.shape[0] != B or q.shape[1] < k or q.shape[2:] != (4, 2) or n.shape != (B,):
+        raise ValueError(f"warp_quads_ref: quads [B, Kq >= k, 4, 2] and count [B] required, got {q.shape}, {n.shape}")
+    patches = np.zeros((B * k, Ho, Wo, 3), np.uint8)
+    valid = np.zeros(B * k, np.int32)
+    f64 = np.float64
+    u = ((2 * np.arange(Wo, dtype=np.int64) + 1) * (8 + m) - m * Wo).astype(f64) / f64(16 * Wo)       # [Wo]
+    v = (((2 * np.arange(Ho, dtype=np.int64) + 1) * (8 + m) - m * Ho).astype(f64) / f64(16 * Ho))[:, None]
+    for b in range(B):
+        for i in range(min(max(int(n[b]), 0), k)):
+            if q[b, i].min() < COORD_MIN or q[b, i].max() > COORD_MAX:
+                continue
+            c = warp_coefficients_ref(q[b, i].tolist(), origin)
+            if c is None:
+                continue
+            assert all(abs(x) < 2 ** 53 for x in c)
+            G, Hh, den, A, Bx, Cx, D, E, Cy = (f64(x) for x in c)
+            w = ((G * u) + (Hh * v)) + den                              # [Ho, Wo]
+            X = ((A * u) + (Bx * v)) + Cx
+            Y = ((D * u) + (E * v)) + Cy
+            ok = w > 0
+            with np.errstate(all="ignore"):
+                px, py = X / np.where(ok, w, f64(1)), Y / np.where(ok, w, f64(1))
+                tx = np.minimum(np.maximum(px * f64(128) - f64(127.5), f64(0)), f64((W - 1) * 256))
+                ty = np.minimum(np.maximum(py * f64(128) - f64(127.5), f64(0)), f64((H - 1) * 256))
+            Px, Py = np.floor(tx).astype(np.int64), np.floor(ty).astype(np.int64)
+            xi, fx, yi, fy = Px >> 8, (Px & 255)[..., None], Py >> 8, (Py & 255)[..., None]
+            xj, yj = np.minimum(xi + 1, W - 1), np.minimum(yi + 1, H - 1)
+            p = f[b]
+            out = ((256 - fx) * (256 - fy) * p[yi, xi] + fx * (256 - fy) * p[yi, xj] + (256 - fx) * fy * p[yj, xi]
+                   + fx * fy * p[yj, xj] + 32768) >> 16
+            patches[b * k + i] = np.where(ok[..., None], out, 0).astype(np.uint8)
+            valid[b * k + i] = 1
+    return torch.from_numpy(patches), torch.from_numpy(valid)
