@@ -1,5 +1,6 @@
 // torch.ops.aiko.*: the detect head's tail and what works on its detections (decode, NMS, crop,
-// warp, draw, redact, track), and motion and marker detection, which write detector rows.
+// warp, draw, redact, track), motion and marker detection, which write detector rows, and the
+// camera wall, which is ordered by their counts.
 // Each operator validates shapes / dtypes / devices on the host (checks.h holds the shared
 // checks) and launches on the caller's current HIP stream.
 #include "checks.h"
@@ -432,6 +433,72 @@ void marker_detect_out(const at::Tensor& frames, int64_t modules, int64_t cell, 
                "marker_detect");
 }
 
+// The camera wall (wall_ops.hip; the rule is in ops/wall.py): frames [B, H, W, 3] and, optionally,
+// score int32 [B] -> wall [P, rows tile_h + (rows + 1) gap, cols tile_w + (cols + 1) gap, 3] and the
+// camera of every tile in source [P, rows cols].  order 0 index, 1 score.  Colours are packed
+// R | G << 8 | B << 16.  passes: 3, or the bits of the launches to run alone (measurements: 1 the
+// selection, 2 the composition from the source the caller filled).  Two launches on the current stream
+void frame_wall_out(const at::Tensor& frames, const c10::optional<at::Tensor>& score, int64_t rows, int64_t cols,
+                    int64_t tile_h, int64_t tile_w, int64_t gap, int64_t order, int64_t min_score, int64_t ring,
+                    int64_t label_scale, int64_t label_base, int64_t background, int64_t alert, int64_t label_fg,
+                    int64_t label_bg, int64_t passes, at::Tensor& wall, at::Tensor& source) {
+  check_cuda_all({&frames, &wall, &source}, {"frames", "wall", "source"});
+  check_same_device({&frames}, {&wall, &source}, "frame_wall_out");
+  check_frames_u8(frames, "frame_wall_out");
+  TORCH_CHECK(frames.numel() >= 3, "aiko.frame_wall_out: frames uint8 [B, H, W, 3] contiguous required");
+  const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2);
+  TORCH_CHECK(B <= INT_MAX && H * W <= (1 << 23), "aiko.frame_wall_out: H * W = ", H * W,
+              " exceeds 2^23 pixels per frame (the 32-bit sums of the area average)");
+  TORCH_CHECK(rows >= 1 && cols >= 1 && rows * cols <= 1024, "aiko.frame_wall_out: rows, cols >= 1 and rows * cols "
+              "<= 1024 tiles per page required, got ", rows, " x ", cols);
+  TORCH_CHECK(tile_h >= 1 && tile_h <= H && tile_w >= 1 && tile_w <= W, "aiko.frame_wall_out: a tile of 1..", H,
+              " x 1..", W, " required (the wall never enlarges), got ", tile_h, " x ", tile_w);
+  TORCH_CHECK(gap >= 0 && gap <= 64, "aiko.frame_wall_out: 0 <= gap <= 64 required, got ", gap);
+  TORCH_CHECK(order == 0 || order == 1, "aiko.frame_wall_out: order 0 (index) or 1 (score) required, got ", order);
+  TORCH_CHECK(min_score >= INT_MIN && min_score <= INT_MAX, "aiko.frame_wall_out: min_score must fit int32");
+  TORCH_CHECK(ring >= 0 && 2 * ring <= std::min(tile_h, tile_w), "aiko.frame_wall_out: 0 <= 2 ring <= min(tile) "
+              "required, got ring ", ring);
+  TORCH_CHECK(label_scale >= 0 && label_scale <= 4, "aiko.frame_wall_out: 0 <= label_scale <= 4 required, got ",
+              label_scale);
+  TORCH_CHECK(label_base >= 0 && label_base + B <= INT_MAX, "aiko.frame_wall_out: label_base >= 0 with label_base + "
+              "B <= 2^31 - 1 required, got ", label_base);
+  for (int64_t c : {background, alert, label_fg, label_bg})
+    TORCH_CHECK(c >= 0 && c <= 0xffffff, "aiko.frame_wall_out: colour components 0..255 (packed R | G << 8 | B << "
+                "16) required, got ", c);
+  TORCH_CHECK(passes >= 1 && passes <= 3, "aiko.frame_wall_out: passes in 1..3 required, got ", passes);
+  const int* score_p = nullptr;
+  if (defined(score)) {
+    check_cuda(*score, "score");
+    check_same_device({&frames}, {&*score}, "frame_wall_out");
+    TORCH_CHECK(score->scalar_type() == at::kInt && score->dim() == 1 && score->size(0) == B && score->is_contiguous(),
+                "aiko.frame_wall_out: score int32 [B] = [", B, "] contiguous required");
+    score_p = score->data_ptr<int>();
+  }
+  TORCH_CHECK(order == 0 || score_p, "aiko.frame_wall_out: score order requires a score");
+  TORCH_CHECK(order == 0 || B <= 4096, "aiko.frame_wall_out: score order ranks at most 4096 cameras, got ", B);
+  const int64_t N = rows * cols;
+  const int64_t Hw = rows * tile_h + (rows + 1) * gap, Ww = cols * tile_w + (cols + 1) * gap;
+  TORCH_CHECK(wall.scalar_type() == at::kByte && wall.dim() == 4 && wall.size(0) >= 1 && wall.size(1) == Hw &&
+                  wall.size(2) == Ww && wall.size(3) == 3 && wall.is_contiguous(),
+              "aiko.frame_wall_out: wall uint8 [P >= 1, ", Hw, ", ", Ww, ", 3] contiguous required");
+  const int64_t P = wall.size(0);
+  TORCH_CHECK(Hw <= (1 << 24) && Ww <= (1 << 24) && P * N < (1 << 24), "aiko.frame_wall_out: a wall of ", P, " x ", Hw,
+              " x ", Ww, " exceeds the limits (side <= 2^24, pages * tiles < 2^24)");
+  TORCH_CHECK(source.scalar_type() == at::kInt && source.dim() == 2 && source.size(0) == P && source.size(1) == N &&
+                  source.is_contiguous(),
+              "aiko.frame_wall_out: source int32 [P, rows * cols] = [", P, ", ", N, "] contiguous required");
+  // no output may overlap an input or the other output
+  if (score_p)
+    check_no_overlap({&wall, &source}, {"wall", "source"}, {&frames, &*score}, {"frames", "score"}, "frame_wall_out");
+  else
+    check_no_overlap({&wall, &source}, {"wall", "source"}, {&frames}, {"frames"}, "frame_wall_out");
+  check_launch(aiko_frame_wall(frames.data_ptr(), score_p, source.data_ptr<int>(), wall.data_ptr(), (int)B, (int)H,
+                               (int)W, (int)rows, (int)cols, (int)tile_h, (int)tile_w, (int)gap, (int)P, (int)order,
+                               (int)min_score, (int)ring, (int)label_scale, (int)label_base, (int)background,
+                               (int)alert, (int)label_fg, (int)label_bg, (int)passes, cur_stream()),
+               "frame_wall");
+}
+
 }  // namespace
 
 TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
@@ -444,4 +511,5 @@ TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("track_detections_out", &track_detections_out);
   m.impl("motion_detect_out", &motion_detect_out);
   m.impl("marker_detect_out", &marker_detect_out);
+  m.impl("frame_wall_out", &frame_wall_out);
 }

@@ -30,6 +30,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("track_detections_out(Tensor det, Tensor count, Tensor boxes, Tensor meta, Tensor issued, int k, float iou, int max_age, float min_score, bool class_aware, int label_mod, Tensor(a!) boxes_out, Tensor(b!) meta_out, Tensor(c!) issued_out, Tensor(d!) ids, Tensor(e!) hits, Tensor(f!) labels) -> ()");
   m.def("marker_detect_out(Tensor frames, int modules, int cell, int contrast, int min_side, int max_cand, int passes, Tensor(a!) det, Tensor(b!) count, Tensor(c!) corners, Tensor(d!) ids, Tensor(e!) cands, Tensor(f!) mask, Tensor(g!) work) -> ()");
   m.def("motion_detect_out(Tensor frames, Tensor bg, Tensor seen, int cell, int threshold, int learn_shift, bool learn_moving, int warmup, int min_cells, Tensor(a!) bg_out, Tensor(b!) seen_out, Tensor(c!) det, Tensor(d!) count, Tensor(e!) mask, Tensor(f!) cells) -> ()");
+  m.def("frame_wall_out(Tensor frames, Tensor? score, int rows, int cols, int tile_h, int tile_w, int gap, int order, int min_score, int ring, int label_scale, int label_base, int background, int alert, int label_fg, int label_bg, int passes, Tensor(a!) wall, Tensor(b!) source) -> ()");
   m.def("voice_activity_out(Tensor audio, Tensor state, int frame, int threshold, int min_level, int up_shift, int speech_shift, int down_shift, int warmup, int attack, int hang, int max_zc, int window, Tensor(a!) state_out, Tensor(b!) level, Tensor(c!) zc, Tensor(d!) mask, Tensor(e!) seg, Tensor(f!) count, Tensor(g!) speech, Tensor(h!) silent) -> ()");
   m.def("spectrum_out(Tensor audio, Tensor window, Tensor twiddle, Tensor band_start, int n_fft, int hop, float inv_F, float lo, float hi, int k_lo, int k_hi, bool local, Tensor(a!) power, Tensor(b!) amplitudes, Tensor(c!) band_amplitudes, Tensor(d!) peak_bins, Tensor(e!) peak_amplitudes, Tensor(f!) peak_counts) -> ()");
   m.def("spectrum_graph_out(Tensor peak_bins, Tensor peak_amplitudes, Tensor peak_counts, Tensor bin_px, float y_max, int[] color, Tensor(a!) image) -> ()");

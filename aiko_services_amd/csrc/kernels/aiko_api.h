@@ -128,6 +128,15 @@ int aiko_motion_detect(const void* frames, const int* bg, const int* seen, int* 
                        int* count, void* mask, int* cells, int B, int H, int W, int cell, int threshold,
                        int learn_shift, int learn_moving, int warmup, int min_cells, int max_det, hipStream_t stream);
 
+// ---- wall_ops.hip: the camera wall (aiko_frame_wall = the selection + the composition)
+int aiko_wall_select(const int* score, int* source, int B, long slots, int order, int min_score, hipStream_t stream);
+int aiko_wall_compose(const void* frames, const int* score, const int* source, void* wall, int B, int H, int W, int R,
+                      int C, int th, int tw, int g, int P, int min_score, int ring, int label_scale, int label_base,
+                      int background, int alert, int label_fg, int label_bg, hipStream_t stream);
+int aiko_frame_wall(const void* frames, const int* score, int* source, void* wall, int B, int H, int W, int R, int C,
+                    int th, int tw, int g, int P, int order, int min_score, int ring, int label_scale, int label_base,
+                    int background, int alert, int label_fg, int label_bg, int passes, hipStream_t stream);
+
 // ---- marker_ops.hip: square markers
 int aiko_marker_detect(const void* frames, float* det, int* count, int* corners, int* ids, int* cands, void* mask,
                        void* work, int B, int H, int W, int N, int cell, int contrast, int min_side, int max_cand,

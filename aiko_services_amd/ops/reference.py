@@ -1339,3 +1339,86 @@ def warp_quads_ref(frames: torch.Tensor, quads: torch.Tensor, count: torch.Tenso
             patches[b * k + i] = np.where(ok[..., None], out, 0).astype(np.uint8)
             valid[b * k + i] = 1
     return torch.from_numpy(patches), torch.from_numpy(valid)
+
+
+# ---- camera wall ----------------------------------------------------------------------------
+
+def wall_weights_ref(full: int, tile: int):
+    """int64 ``[tile, full]``: ``w[o, j] = max(0, min((j+1)*tile, (o+1)*full) - max(j*tile, o*full))``,
+    the share of source pixel ``j`` in output pixel ``o`` of an axis of ``full`` pixels reduced to
+    ``tile``, in units of ``1 / (full*tile)`` of the axis.  Every row sums to ``full``."""
+    import numpy as np
+    o = np.arange(tile, dtype=np.int64)[:, None]
+    j = np.arange(full, dtype=np.int64)[None, :]
+    return np.maximum(0, np.minimum((j + 1) * tile, (o + 1) * full) - np.maximum(j * tile, o * full))
+
+
+def wall_select_ref(score, batch: int, slots: int, order: str = "index", min_score: int = 1) -> list:
+    """The camera of every slot, or -1: ``ops.wall``'s selection rule."""
+    if order == "index":
+        cams = list(range(batch))
+    elif order == "score":
+        s = [int(v) for v in score.tolist()]
+        cams = sorted((b for b in range(batch) if s[b] >= min_score), key=lambda b: (-s[b], b))
+    else:
+        raise ValueError(f"wall_select_ref: unknown order {order!r}")
+    return [cams[j] if j < len(cams) else -1 for j in range(slots)]
+
+
+def frame_wall_ref(frames: torch.Tensor, score: torch.Tensor | None = None, *, rows: int, cols: int, tile,
+                   gap: int = 0, pages: int = 1, order: str = "index", min_score: int = 1, ring: int = 0,
+                   label_scale: int = 0, label_base: int = 0, background=(0, 0, 0), alert=(255, 0, 0),
+                   label_fg=(255, 255, 255), label_bg=(0, 0, 0)):
+    """``ops.wall.frame_wall`` with numpy int64 on the CPU, from the rule in that module's docstring:
+    the selection as a sorted list, each shown tile as ``wy @ frame @ wx^T`` with the weights of
+    :func:`wall_weights_ref` and one rounding, then ring and label painted over it.  Returns
+    ``(wall, source)``: uint8 ``[pages, Hw, Ww, 3]`` and int32 ``[pages, rows*cols]``."""
+    import numpy as np
+    from . import overlay_font
+    from .wall import check_parameters, wall_shape
+    frames = frames.cpu()
+    B, H, W, _ = frames.shape
+    th, tw = (int(v) for v in tile)
+    check_parameters(rows=rows, cols=cols, tile=(th, tw), gap=gap, pages=pages, order=order, min_score=min_score,
+                     ring=ring, label_scale=label_scale, label_base=label_base, background=background, alert=alert,
+                     label_fg=label_fg, label_bg=label_bg, frame=(H, W))
+    if order == "score" and score is None:
+        raise ValueError("frame_wall_ref: order 'score' requires a score")
+    if score is not None:
+        score = score.cpu()
+        if tuple(score.shape) != (B,):
+            raise ValueError(f"frame_wall_ref: score [{B}] required, got {tuple(score.shape)}")
+    N, g, q, s = rows * cols, int(gap), int(ring), int(label_scale)
+    Hw, Ww = wall_shape(rows, cols, (th, tw), g)
+    source = wall_select_ref(score, B, pages * N, order, int(min_score))
+    wall = np.empty((pages, Hw, Ww, 3), np.uint8)
+    wall[:] = np.asarray(background, np.uint8)
+    wy, wx = wall_weights_ref(H, th), wall_weights_ref(W, tw)               # [th, H], [tw, W]
+    f = frames.numpy()
+    for slot, cam in enumerate(source):
+        if cam < 0:
+            continue
+        p, t = divmod(slot, N)
+        oy, ox = g + (t // cols) * (th + g), g + (t % cols) * (tw + g)
+        S = np.tensordot(wy, f[cam].astype(np.int64), axes=(1, 0))          # rows: int64 [th, W, 3]
+        S = np.tensordot(S, wx, axes=(1, 1)).transpose(0, 2, 1)             # columns: [th, tw, 3]
+        tile_px = ((2 * S + W * H) // (2 * W * H)).astype(np.uint8)
+        if q > 0 and score is not None and int(score[cam]) >= int(min_score):
+            i, j = np.arange(th)[:, None], np.arange(tw)[None, :]
+            edge = np.minimum(np.minimum(i, j), np.minimum(th - 1 - i, tw - 1 - j)) < q
+            tile_px[edge] = np.asarray(alert, np.uint8)
+        if s > 0:
+            text = str(int(label_base) + cam)
+            box = np.empty((s + 8 * s, s + len(text) * 6 * s, 3), np.uint8)
+            box[:] = np.asarray(label_bg, np.uint8)
+            for n, ch in enumerate(text):
+                for gy, bits in enumerate(overlay_font.glyph_rows(ch)):
+                    for gx in range(overlay_font.CELL_W):
+                        if bits & (0x80 >> gx):
+                            y0, x0 = s + gy * s, s + (n * 6 + gx) * s
+                            box[y0:y0 + s, x0:x0 + s] = np.asarray(label_fg, np.uint8)
+            hh, ww = min(box.shape[0], th - q), min(box.shape[1], tw - q)      # clipped to the tile
+            if hh > 0 and ww > 0:
+                tile_px[q:q + hh, q:q + ww] = box[:hh, :ww]
+        wall[p, oy:oy + th, ox:ox + tw] = tile_px
+    return torch.from_numpy(wall), torch.tensor(source, dtype=torch.int32).view(pages, N)
