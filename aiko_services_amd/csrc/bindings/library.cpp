@@ -7,6 +7,7 @@ TORCH_LIBRARY(aiko, m) {
   m.def("preprocess_out(Tensor frames, Tensor(a!) out, int Ho, int Wo, int pad_t, int pad_l, float[] mean, float[] std, bool bgr, float[] canvas=[]) -> ()");
   m.def("upsample2x_out(Tensor x, Tensor(a!) y) -> ()");
   m.def("resize_u8_out(Tensor x, Tensor(a!) y) -> ()");
+  m.def("scale_frames_out(Tensor frames, Tensor? hb, Tensor? hk, Tensor? vb, Tensor? vk, int tile_rows, int tile_cols, int win_rows, Tensor(a!) out) -> ()");
   m.def("roi_crop_out(Tensor frames, Tensor det, Tensor count, int k, float margin, Tensor(a!) crops, Tensor(b!) rois) -> ()");
   m.def("quad_warp_out(Tensor frames, Tensor quads, Tensor count, int k, int margin, int origin, Tensor(a!) patches, Tensor(b!) valid) -> ()");
   m.def("draw_detections_out(Tensor frames, Tensor det, Tensor count, int k, Tensor? labels, Tensor? scores, Tensor names, Tensor font, Tensor palette, int glyph_width, int thickness, int text_scale, float margin, bool show_score, Tensor(a!) out) -> ()");

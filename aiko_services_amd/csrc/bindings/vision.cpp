@@ -48,6 +48,79 @@ void resize_u8_out(const at::Tensor& x, at::Tensor& y) {
                "resize_u8");
 }
 
+// One axis of a scale plan (ops/scale.py): bounds int32 [n_out, 2] and coefficients int32
+// [n_out, ksize], both given or both left out (then the axis keeps its size).  Returns ksize, or 0
+// without the pass.  What the tables hold (first + n <= in_size per entry) is checked on the host
+// when the plan is made; here they lie in HBM, and the kernel clamps what it reads from them.
+int64_t check_scale_axis(const at::Tensor& frames, const c10::optional<at::Tensor>& bounds,
+                         const c10::optional<at::Tensor>& coeffs, int64_t n_in, int64_t n_out, const char* axis) {
+  TORCH_CHECK(defined(bounds) == defined(coeffs), "aiko.scale_frames_out: the ", axis,
+              " bounds and coefficients are given together or not at all");
+  if (!defined(bounds)) {
+    TORCH_CHECK(n_out == n_in, "aiko.scale_frames_out: without a ", axis, " plan out keeps that size, ", n_in,
+                ", got ", n_out);
+    return 0;
+  }
+  check_cuda_all({&*bounds, &*coeffs}, {"bounds", "coefficients"});
+  check_same_device({&frames}, {&*bounds, &*coeffs}, "scale_frames_out");
+  TORCH_CHECK(bounds->scalar_type() == at::kInt && bounds->dim() == 2 && bounds->size(0) == n_out &&
+                  bounds->size(1) == 2 && bounds->is_contiguous() && aligned(*bounds, 8),
+              "aiko.scale_frames_out: ", axis, " bounds int32 [", n_out, ", 2] contiguous, 8-byte aligned required");
+  TORCH_CHECK(coeffs->scalar_type() == at::kInt && coeffs->dim() == 2 && coeffs->size(0) == n_out &&
+                  coeffs->size(1) >= 1 && coeffs->size(1) <= INT_MAX && coeffs->is_contiguous(),
+              "aiko.scale_frames_out: ", axis, " coefficients int32 [", n_out, ", ksize >= 1] contiguous required");
+  return coeffs->size(1);
+}
+
+// The antialiased resize (scale_ops.hip; the rule is in ops/scale.py): frames [B, H, W, 3] -> out
+// [B, Ho, Wo, 3] by the horizontal plan (hb, hk) and the vertical plan (vb, vk).  With both, a
+// workgroup makes tile_rows x tile_cols output pixels from at most win_rows source rows.
+void scale_frames_out(const at::Tensor& frames, const c10::optional<at::Tensor>& hb,
+                      const c10::optional<at::Tensor>& hk, const c10::optional<at::Tensor>& vb,
+                      const c10::optional<at::Tensor>& vk, int64_t tile_rows, int64_t tile_cols, int64_t win_rows,
+                      at::Tensor& out) {
+  check_cuda_all({&frames, &out}, {"frames", "out"});
+  check_same_device({&frames}, {&out}, "scale_frames_out");
+  check_frames_u8(frames, "scale_frames_out");
+  const int64_t B = frames.size(0), H = frames.size(1), W = frames.size(2);
+  const int64_t side = 1 << 24;
+  TORCH_CHECK(B >= 1 && B <= 65535 && H >= 1 && W >= 1 && H <= side && W <= side,
+              "aiko.scale_frames_out: 1..65535 frames with sides 1..2^24 required, got ", B, " x ", H, " x ", W);
+  TORCH_CHECK(out.scalar_type() == at::kByte && out.dim() == 4 && out.size(0) == B && out.size(1) >= 1 &&
+                  out.size(2) >= 1 && out.size(1) <= side && out.size(2) <= side && out.size(3) == 3 &&
+                  out.is_contiguous(),
+              "aiko.scale_frames_out: out uint8 [", B, ", Ho, Wo, 3] contiguous with sides 1..2^24 required");
+  const int64_t Ho = out.size(1), Wo = out.size(2);
+  const int64_t ksh = check_scale_axis(frames, hb, hk, W, Wo, "horizontal");
+  const int64_t ksv = check_scale_axis(frames, vb, vk, H, Ho, "vertical");
+  TORCH_CHECK(ksh > 0 || ksv > 0, "aiko.scale_frames_out: no pass to run (out has the frames' size): copy instead");
+  if (ksh > 0 && ksv > 0) {
+    TORCH_CHECK(tile_rows >= 1 && tile_rows <= Ho && tile_cols >= 4 && tile_cols <= 64 && tile_cols % 4 == 0,
+                "aiko.scale_frames_out: a tile of 1..Ho rows and 4..64 columns, a multiple of 4, required, got ",
+                tile_rows, " x ", tile_cols);
+    TORCH_CHECK(win_rows >= 1 && win_rows <= H && win_rows * tile_cols * 3 <= 160 * 1024,
+                "aiko.scale_frames_out: a window of 1..H rows that fits 160 KiB of LDS required, got ", win_rows,
+                " rows x ", tile_cols, " columns");
+  }
+  std::vector<const at::Tensor*> ins = {&frames};
+  std::vector<const char*> in_names = {"frames"};
+  if (ksh > 0) {
+    ins.insert(ins.end(), {&*hb, &*hk});
+    in_names.insert(in_names.end(), {"the horizontal bounds", "the horizontal coefficients"});
+  }
+  if (ksv > 0) {
+    ins.insert(ins.end(), {&*vb, &*vk});
+    in_names.insert(in_names.end(), {"the vertical bounds", "the vertical coefficients"});
+  }
+  check_no_overlap({&out}, {"out"}, ins, in_names, "scale_frames_out");
+  check_launch(aiko_scale_frames(frames.data_ptr(), ksh ? hb->data_ptr<int>() : nullptr,
+                                 ksh ? hk->data_ptr<int>() : nullptr, ksv ? vb->data_ptr<int>() : nullptr,
+                                 ksv ? vk->data_ptr<int>() : nullptr, out.data_ptr(), (int)B, (int)H, (int)W, (int)Ho,
+                                 (int)Wo, (int)ksh, (int)ksv, (int)tile_rows, (int)tile_cols, (int)win_rows,
+                                 cur_stream()),
+               "scale_frames");
+}
+
 void maxpool_out(const at::Tensor& x, at::Tensor& y, int64_t k, int64_t s, int64_t p) {
   check_cuda(x, "x");
   check_cuda(y, "y");
@@ -167,6 +240,7 @@ void window_shift_out(const at::Tensor& src, const at::Tensor& chunk, at::Tensor
 TORCH_LIBRARY_IMPL(aiko, CUDA, m) {
   m.impl("preprocess_out", &preprocess_out);
   m.impl("resize_u8_out", &resize_u8_out);
+  m.impl("scale_frames_out", &scale_frames_out);
   m.impl("maxpool_out", &maxpool_out);
   m.impl("avgpool_out", &avgpool_out);
   m.impl("mean_rows_out", &mean_rows_out);

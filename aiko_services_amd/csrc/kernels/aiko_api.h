@@ -137,6 +137,11 @@ int aiko_frame_wall(const void* frames, const int* score, int* source, void* wal
                     int th, int tw, int g, int P, int order, int min_score, int ring, int label_scale, int label_base,
                     int background, int alert, int label_fg, int label_bg, int passes, hipStream_t stream);
 
+// ---- scale_ops.hip: the antialiased fixed-point resize (null bounds = that pass is left out)
+int aiko_scale_frames(const void* frames, const int* hb, const int* hk, const int* vb, const int* vk, void* out, int B,
+                      int H, int W, int Ho, int Wo, int ksh, int ksv, int tile_rows, int tile_cols, int win_rows,
+                      hipStream_t stream);
+
 // ---- marker_ops.hip: square markers
 int aiko_marker_detect(const void* frames, float* det, int* count, int* corners, int* ids, int* cands, void* mask,
                        void* work, int B, int H, int W, int N, int cell, int contrast, int min_side, int max_cand,

@@ -122,7 +122,14 @@ class ImageSynthetic(PipelineElement):
 
 class ImageResize(PipelineElement):
     """``resolution`` = ``"WxH"``.  Host images (PIL / numpy) resize bilinearly on the CPU; a
-    device uint8 batch ``[B, H, W, 3]`` is resized on the GPU by the HIP kernel."""
+    device uint8 batch ``[B, H, W, 3]`` is resized on the GPU by the two-tap HIP kernel.
+
+    With the optional ``filter`` (``box``, ``bilinear``, ``hamming``, ``bicubic`` or ``lanczos``) both
+    branches resize with that antialiasing filter instead, the host one through Pillow and the device
+    one through ``ops.scale.scale_frames``, and return identical bytes."""
+
+    PIL_FILTERS = {"box": "BOX", "bilinear": "BILINEAR", "hamming": "HAMMING", "bicubic": "BICUBIC",
+                   "lanczos": "LANCZOS"}
 
     def __init__(self, context):
         context.set_protocol("image_resize:0")
@@ -133,15 +140,26 @@ class ImageResize(PipelineElement):
         if not found:
             return StreamEvent.ERROR, {"diagnostic": 'Must provide "resolution" parameter'}
         width, height = (int(v) for v in str(resolution).lower().split("x"))
+        name, filtered = self.get_parameter("filter")
+        if filtered and str(name) not in self.PIL_FILTERS:
+            return StreamEvent.ERROR, {"diagnostic": f'"filter" must be one of {sorted(self.PIL_FILTERS)}, '
+                                                     f"got {name!r}"}
         if hasattr(images, "is_cuda") and images.is_cuda:
+            if filtered:
+                from ...ops.scale import scale_frames
+                try:
+                    return StreamEvent.OKAY, {"images": scale_frames(images.contiguous(), (height, width), str(name))}
+                except ValueError as exc:
+                    return StreamEvent.ERROR, {"diagnostic": f"ImageResize: {exc}"}
             from ...ops.vision import resize_u8
             return StreamEvent.OKAY, {"images": resize_u8(images, (height, width))}
+        resample = getattr(Image, self.PIL_FILTERS[str(name)]) if filtered else Image.BILINEAR
         out = []
         for image in images:
             if isinstance(image, np.ndarray):
-                out.append(np.asarray(Image.fromarray(image).resize((width, height), Image.BILINEAR)))
+                out.append(np.asarray(Image.fromarray(image).resize((width, height), resample)))
             else:
-                out.append(image.resize((width, height), Image.BILINEAR))
+                out.append(image.resize((width, height), resample))
         return StreamEvent.OKAY, {"images": out}
 
 

@@ -56,11 +56,12 @@ def require_native() -> None:
 
 from .conv import (ConvSpec, conv2d, linear, make_conv_spec, make_linear_spec,  # noqa: E402
                    make_stem_spec, stem_geometry)
+from .scale import scale_frames, scale_plan  # noqa: E402
 from .vision import avgpool, maxpool2d, preprocess_frames, softmax_topk  # noqa: E402
 
 __all__ = [
     "ConvSpec", "avgpool", "conv2d", "linear", "load_native", "make_conv_spec",
     "make_linear_spec", "make_stem_spec", "maxpool2d", "native_available",
-    "native_library_path", "preprocess_frames", "require_native", "softmax_topk",
-    "stem_geometry",
+    "native_library_path", "preprocess_frames", "require_native", "scale_frames", "scale_plan",
+    "softmax_topk", "stem_geometry",
 ]

@@ -1422,3 +1422,40 @@ def frame_wall_ref(frames: torch.Tensor, score: torch.Tensor | None = None, *, r
                 tile_px[q:q + hh, q:q + ww] = box[:hh, :ww]
         wall[p, oy:oy + th, ox:ox + tw] = tile_px
     return torch.from_numpy(wall), torch.tensor(source, dtype=torch.int32).view(pages, N)
+
+
+# ---- antialiased resize ---------------------------------------------------------------------
+
+def scale_pass_sums_ref(pixels, bounds, k, axis: int):
+    """One pass of ``ops.scale``'s rule before the clamp: int64 ``(2**21 + sum_x k[x] * p[first + x])
+    >> 22`` along ``axis`` of the integer array ``pixels``, one output position at a time."""
+    import numpy as np
+    p = np.moveaxis(np.asarray(pixels).astype(np.int64), axis, 0)
+    out = np.empty((bounds.shape[0],) + p.shape[1:], np.int64)
+    for xx in range(bounds.shape[0]):
+        first, n = int(bounds[xx, 0]), int(bounds[xx, 1])
+        acc = np.full(p.shape[1:], 1 << 21, np.int64)
+        for x in range(n):
+            acc += int(k[xx, x]) * p[first + x]
+        out[xx] = acc >> 22
+    return np.moveaxis(out, 0, axis)
+
+
+def scale_frames_ref(frames: torch.Tensor, size, filter: str = "bicubic", box=None) -> torch.Tensor:
+    """``ops.scale.scale_frames`` with numpy int64 on the CPU, from the rule in that module's
+    docstring and with its :func:`~aiko_services_amd.ops.scale.axis_plan`: the horizontal pass over
+    every source row, clamped to uint8, then the vertical pass on that; a pass the rule leaves out is
+    left out.  ``box`` = (left, top, right, bottom) in sixteenths.  Returns a new uint8
+    ``[B, Ho, Wo, 3]`` tensor."""
+    import numpy as np
+    from .scale import axis_plans
+    frames = frames.cpu()
+    if frames.dim() != 4 or frames.shape[3] != 3 or frames.dtype != torch.uint8:
+        raise ValueError("scale_frames_ref: frames uint8 [B, H, W, 3] required")
+    horizontal, vertical = axis_plans(int(frames.shape[1]), int(frames.shape[2]), size, filter, box)
+    p = frames.numpy()
+    if horizontal is not None:
+        p = np.clip(scale_pass_sums_ref(p, *horizontal, axis=2), 0, 255).astype(np.uint8)
+    if vertical is not None:
+        p = np.clip(scale_pass_sums_ref(p, *vertical, axis=1), 0, 255).astype(np.uint8)
+    return torch.from_numpy(np.ascontiguousarray(p).copy())
